@@ -2,8 +2,20 @@
 (BASELINE.json metric), MovieLens-full shape, k = 64, on MI355X.
 
     python bench.py [--gpus N] [--steps 20] [--warmup 5] [--k 64]
-                    [--shape ml-full|c5] [--scale S] [--solver cg|cholesky] [--no-cpu]
+                    [--shape ml-full|c5] [--scale S] [--solver cg|cholesky]
+                    [--dump-outputs DIR] [--full [--no-cpu]]
                     [--comm rccl|gloo] [--device-map 0,0]
+
+A plain run does what the headline figure needs and no more: it builds the
+context, warms up, times ``--steps`` ALS iterations and prints the result line
+(the contract fields, ``config``, the CG iteration counts of the timed steps
+and the arithmetic ``iteration_roofline``).  ``--dump-outputs DIR`` also
+writes what the last timed step left -- the factor tables ``get_factors()``
+returns -- as ``DIR/U.npy`` and ``DIR/V.npy``; data and start are seeded, so
+two builds can be compared output for output.  Everything else described
+below (``roofline`` and the kernel table from the instrumented replay,
+``cpu_baseline``, ``same_window``, ``trajectory``, the sharded
+``decomposition``) takes runs of its own and is measured only with ``--full``.
 
 ``--gpus N`` (N > 1) without a launcher starts the N ranks itself:
 ``torch.distributed.run --nproc-per-node N bench.py ...`` as a child
@@ -24,8 +36,8 @@ For N > 1 it runs under torch.distributed.run, one rank per GPU, users and
 items sharded by rating count (weak scaling is not available for a fixed
 data set: per-rank work shrinks as N grows -> "strong").
 
-Printed on rank 0: ONE JSON line with the contract fields plus
-``roofline`` (dominant kernel, from HIP events on the engine's stream over an
+Printed on rank 0: ONE JSON line with the contract fields plus, with
+``--full``, ``roofline`` (dominant kernel, from HIP events on the engine's stream over an
 instrumented replay of the timed steps; the timed region itself carries no
 per-launch events), ``cpu_baseline`` (the reference library compiled from
 /root/reference sources, oracle/_ref/cpp_ls_lib.so, timed on the same data
@@ -68,15 +80,23 @@ def load_data(shape, k, cache_dir="/tmp", scale=1.0):
     tag = "" if scale == 1.0 else f"_x{scale:g}"
     path = os.path.join(cache_dir, f"mr_bench_{shape}{tag}_k{k}_{synth.DATA_SEED}.npz")
     if os.path.exists(path):
-        with np.load(path, allow_pickle=False) as d:
-            rs = synth.RatingSet(d["u"], d["i"], d["r"], int(d["nu"]), int(d["ni"]), k)
-            return rs
+        try:
+            with np.load(path, allow_pickle=False) as d:
+                rs = synth.RatingSet(d["u"], d["i"], d["r"], int(d["nu"]), int(d["ni"]), k)
+                return rs
+        except Exception as e:  # unreadable or damaged cache: generate again
+            log(f"[bench] data cache {path} not usable ({e!r}); regenerating")
     rs = synth.movielens_like(shape, k, scale=scale)
+    part = f"{path[:-4]}.{os.getpid()}.part.npz"   # whole or absent for a concurrent reader
     try:
-        np.savez(path, u=rs.user_ids, i=rs.item_ids, r=rs.ratings, nu=rs.num_users,
+        np.savez(part, u=rs.user_ids, i=rs.item_ids, r=rs.ratings, nu=rs.num_users,
                  ni=rs.num_items)
+        os.replace(part, path)
     except OSError:
-        pass
+        try:
+            os.remove(part)
+        except OSError:
+            pass
     return rs
 
 
@@ -328,6 +348,110 @@ def step_decomposition(st, steps, elapsed, ctx, k, world, dist, events_ms):
                               "peer reductions at the xGMI latency (DESIGN.md Multi-GPU)")}}
 
 
+def kernel_report(st, ctx, args, k, world, c5, onepass, n_local_users):
+    """``--full``: the ``roofline`` of the dominant kernel and the ``kernels``
+    table, from the kernel times ``st`` holds (the instrumented replay's)."""
+    # dominant kernel and its roofline (rank 0's kernels, rank 0's shard sizes:
+    # cost-balanced shards are unequal)
+    ldk = (k + 15) // 16 * 16
+    if args.no_kernel_events:
+        st["kernel_ms"] = {"none": 1.0}
+        st["kernel_launches"] = {"none": 1}
+    best = max(st["kernel_ms"].items(), key=lambda kv: kv[1])
+    cls, tot_ms = best
+    launches = max(1, st["kernel_launches"][cls])
+    avg_s = tot_ms / launches / 1e3
+    # work units per launch: a resident CG solve runs all its iterations in
+    # one launch (kernel_units = its CG iterations); 1 for every other class
+    units_per_launch = (st.get("kernel_units", {}).get(cls, launches) or launches) / launches
+    _, nU, _ = ctx.local_size("users")
+    _, nI, n_local_items = ctx.local_size("items")
+    onepass_of = lambda c: onepass  # noqa: E731
+    nbytes, nflops = algorithmic_cost(cls, k, nU, nI, n_local_users, ldk, not args.no_fuse_start,
+                                      n_local_items, onepass_of(cls))
+    nbytes, nflops = nbytes * units_per_launch, nflops * units_per_launch
+    bound = "mfma" if cls.startswith("gram") and k >= 32 else "hbm"
+    if bound == "hbm":
+        achieved, peak, unit = nbytes / avg_s / 1e9, HBM_PEAK_GBS, "GB/s"
+    else:
+        achieved, peak, unit = nflops / avg_s / 1e12, FP32_PEAK_TFS, "TFLOP/s"
+    # Gram kernels: the row gather (k floats of the other side's table per
+    # rating, Infinity-Cache resident) is the binding roofline; peak = the
+    # guide's measured random-row gather rate from a 38 MB table.
+    gather = None
+    if cls.startswith("gram"):
+        gb = (n_local_users if cls == "gram_users" else n_local_items) * 4.0 * k
+        gather = {"bytes_per_launch": int(gb), "achieved_GBps": round(gb / avg_s / 1e9, 1),
+                  "peak_GBps": GATHER_PEAK_GBS, "frac": round(gb / avg_s / 1e9 / GATHER_PEAK_GBS, 3)}
+    traffic = None
+    pmc_path = args.pmc
+    if not pmc_path:   # this round's counter passes, else the previous round's
+        for rnd in ("r06", "r05", "r04"):
+            pmc_path = os.path.join(ROOT, "profiles",
+                                    f"pmc_{rnd}.json" if k == 64 else f"pmc_{rnd}_k{k}.json")
+            if os.path.exists(pmc_path):
+                break
+    if os.path.exists(pmc_path):
+        with open(pmc_path) as f:
+            pmc = json.load(f)
+        # only for the workload the counter passes ran (per-launch bytes)
+        wl = pmc.get("workload", {"shape": "ml-full", "k": 64})
+        if wl.get("shape") == args.shape and wl.get("k") == k and world == 1 and not c5:
+            per = pmc.get("hbm_bytes_per_launch", {})
+            traffic = per.get(cls)
+            if traffic is None and cls.startswith("resident_"):
+                # the resident solve's iterations make the launch-per-iteration
+                # kernel's accesses (the counter passes run that path:
+                # per-launch = per CG iteration) times its iterations per launch
+                it = per.get("matvec_" + cls[len("resident_"):])
+                traffic = None if it is None else int(it * units_per_launch)
+    kernel_table = {}
+    for c, ms in st["kernel_ms"].items():
+        n = st["kernel_launches"][c]
+        if n:
+            u = st.get("kernel_units", {}).get(c, n) or n
+            b, fl = algorithmic_cost(c, k, nU, nI, n_local_users, ldk, not args.no_fuse_start,
+                                     n_local_items, onepass_of(c))
+            b, fl = b * u / n, fl * u / n
+            kernel_table[c] = {"total_ms": round(ms, 3), "launches": n,
+                               "avg_us": round(ms / n * 1e3, 2),
+                               "alg_GBps": round(b / (ms / n / 1e3) / 1e9, 1) if b else None,
+                               "alg_TFps": round(fl / (ms / n / 1e3) / 1e12, 2) if fl else None}
+            if u != n:
+                kernel_table[c]["cg_iterations"] = u
+                kernel_table[c]["us_per_cg_iteration"] = round(ms / u * 1e3, 2)
+    roofline = {"kernel": cls, "bound": bound, "achieved": round(achieved, 2),
+                "peak": peak, "unit": unit, "frac": round(achieved / peak, 4),
+                "traffic": traffic,
+                "alg_bytes_per_launch": int(nbytes), "alg_flops_per_launch": int(nflops),
+                "avg_launch_us": round(avg_s * 1e6, 2), "gather": gather,
+                "units_per_launch": round(units_per_launch, 3)}
+    return roofline, kernel_table
+
+
+DUMP_SEED = 20261019         # rows sampled by --dump-outputs from oversized tables
+DUMP_BUDGET = 64 << 20       # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, ctx):
+    """``--dump-outputs``: the factor tables as ``get_factors()`` returns them
+    after the last timed step, ``path/U.npy`` (users x k+1) and ``path/V.npy``
+    (items x k).  float32 loses nothing: the device tables are fp32 and
+    ``get_factors`` only widens them.  Tables beyond DUMP_BUDGET (C5) are cut
+    to a fixed, seeded sample of rows in proportion."""
+    U, V = ctx.get_factors()
+    tabs = {"U": U.reshape(ctx.num_users, ctx.k + 1), "V": V.reshape(ctx.num_items, ctx.k)}
+    total = sum(t.size for t in tabs.values()) * 4
+    os.makedirs(path, exist_ok=True)
+    for name, t in tabs.items():
+        if total > DUMP_BUDGET:
+            rows = max(1, int(t.shape[0] * DUMP_BUDGET / total))
+            rng = np.random.default_rng(DUMP_SEED)
+            t = t[np.sort(rng.choice(t.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t, dtype=np.float32))
+    log(f"[bench] outputs written to {path}")
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -374,6 +498,13 @@ def main():
                     help="fraction of the shape (users, items, draws); tests and C5 slices")
     ap.add_argument("--solver", default="cg", choices=["cg", "cholesky"])
     ap.add_argument("--ridge", type=float, default=0.0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the factors the last timed step left (get_factors()) as "
+                         "DIR/U.npy and DIR/V.npy, float32 (the device tables' precision)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the instrumented replay "
+                         "(kernel table, roofline), the reference CPU leg, same_window, "
+                         "trajectory and the sharded decomposition")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-onepass", action="store_true",
                     help="CG iteration as matvec + update (two kernels) instead of one pass")
@@ -411,6 +542,8 @@ def main():
                          "profiles/pmc_r06.json at k = 64, profiles/pmc_r06_k<k>.json otherwise; the "
                          "previous round's if absent)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -550,12 +683,15 @@ def main():
     # is deterministic, so the replay runs bit-identical kernels: its CG
     # iteration counts must equal the timed pass's (replay_cg_identical).
     # Tables too large to snapshot (C5) time one instrumented pass instead.
-    instrument = not args.no_kernel_events
+    # A plain run (no --full) stops after the timed region.
+    instrument = args.full and not args.no_kernel_events
     replay = instrument and n_users * (k + 1) + n_items * k < 200_000_000
     snap = ctx.get_factors() if replay else None
     ctx.set_timing(instrument and not replay)
     elapsed = timed_steps()
     st = ctx.stats()
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, ctx)
     events_ms = None
     replay_identical = None
     if replay:
@@ -577,7 +713,7 @@ def main():
     # T(3) - T(1) over repeated pairs; it also hands over the reference's
     # factors after its iteration 1.
     cb = state1 = None
-    cpu_leg = rank == 0 and world == 1 and not args.no_cpu and not c5
+    cpu_leg = args.full and rank == 0 and world == 1 and not args.no_cpu and not c5
     if cpu_leg:
         try:
             cb, state1 = cpu_baseline(args.shape, k, args.cpu_threads, args.cpu_scale * args.scale,
@@ -602,7 +738,7 @@ def main():
     # sums over the timed window must equal the timed region's (the engine is
     # deterministic), which the line checks.
     same_window = trajectory = None
-    if not c5 and not args.no_same_window:
+    if args.full and not c5 and not args.no_same_window:
         if state1 is not None:
             ctx.set_factors(*state1)
         else:
@@ -654,79 +790,11 @@ def main():
     value = total_ratings * args.steps / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
 
-    # dominant kernel and its roofline (rank 0's kernels, rank 0's shard sizes:
-    # cost-balanced shards are unequal)
-    ldk = (k + 15) // 16 * 16
-    if args.no_kernel_events:
-        st["kernel_ms"] = {"none": 1.0}
-        st["kernel_launches"] = {"none": 1}
-    best = max(st["kernel_ms"].items(), key=lambda kv: kv[1])
-    cls, tot_ms = best
-    launches = max(1, st["kernel_launches"][cls])
-    avg_s = tot_ms / launches / 1e3
-    # work units per launch: a resident CG solve runs all its iterations in
-    # one launch (kernel_units = its CG iterations); 1 for every other class
-    units_per_launch = (st.get("kernel_units", {}).get(cls, launches) or launches) / launches
-    _, nU, _ = ctx.local_size("users")
-    _, nI, n_local_items = ctx.local_size("items")
     # one-pass CG on both sides at k <= 128: unsharded or with peer scalars
     # (RCCL collectives: two kernels; Engine::onepass_for)
     onepass = (not args.no_onepass and k <= 128
                and (dist is None or getattr(ctx, "peer_scalars", False)))
-    onepass_of = lambda c: onepass  # noqa: E731
-    nbytes, nflops = algorithmic_cost(cls, k, nU, nI, n_local_users, ldk, not args.no_fuse_start,
-                                      n_local_items, onepass_of(cls))
-    nbytes, nflops = nbytes * units_per_launch, nflops * units_per_launch
-    bound = "mfma" if cls.startswith("gram") and k >= 32 else "hbm"
-    if bound == "hbm":
-        achieved, peak, unit = nbytes / avg_s / 1e9, HBM_PEAK_GBS, "GB/s"
-    else:
-        achieved, peak, unit = nflops / avg_s / 1e12, FP32_PEAK_TFS, "TFLOP/s"
-    # Gram kernels: the row gather (k floats of the other side's table per
-    # rating, Infinity-Cache resident) is the binding roofline; peak = the
-    # guide's measured random-row gather rate from a 38 MB table.
-    gather = None
-    if cls.startswith("gram"):
-        gb = (n_local_users if cls == "gram_users" else n_local_items) * 4.0 * k
-        gather = {"bytes_per_launch": int(gb), "achieved_GBps": round(gb / avg_s / 1e9, 1),
-                  "peak_GBps": GATHER_PEAK_GBS, "frac": round(gb / avg_s / 1e9 / GATHER_PEAK_GBS, 3)}
-    traffic = None
-    pmc_path = args.pmc
-    if not pmc_path:   # this round's counter passes, else the previous round's
-        for rnd in ("r06", "r05", "r04"):
-            pmc_path = os.path.join(ROOT, "profiles",
-                                    f"pmc_{rnd}.json" if k == 64 else f"pmc_{rnd}_k{k}.json")
-            if os.path.exists(pmc_path):
-                break
-    if os.path.exists(pmc_path):
-        with open(pmc_path) as f:
-            pmc = json.load(f)
-        # only for the workload the counter passes ran (per-launch bytes)
-        wl = pmc.get("workload", {"shape": "ml-full", "k": 64})
-        if wl.get("shape") == args.shape and wl.get("k") == k and world == 1 and not c5:
-            per = pmc.get("hbm_bytes_per_launch", {})
-            traffic = per.get(cls)
-            if traffic is None and cls.startswith("resident_"):
-                # the resident solve's iterations make the launch-per-iteration
-                # kernel's accesses (the counter passes run that path:
-                # per-launch = per CG iteration) times its iterations per launch
-                it = per.get("matvec_" + cls[len("resident_"):])
-                traffic = None if it is None else int(it * units_per_launch)
-    kernel_table = {}
-    for c, ms in st["kernel_ms"].items():
-        n = st["kernel_launches"][c]
-        if n:
-            u = st.get("kernel_units", {}).get(c, n) or n
-            b, fl = algorithmic_cost(c, k, nU, nI, n_local_users, ldk, not args.no_fuse_start,
-                                     n_local_items, onepass_of(c))
-            b, fl = b * u / n, fl * u / n
-            kernel_table[c] = {"total_ms": round(ms, 3), "launches": n,
-                               "avg_us": round(ms / n * 1e3, 2),
-                               "alg_GBps": round(b / (ms / n / 1e3) / 1e9, 1) if b else None,
-                               "alg_TFps": round(fl / (ms / n / 1e3) / 1e12, 2) if fl else None}
-            if u != n:
-                kernel_table[c]["cg_iterations"] = u
-                kernel_table[c]["us_per_cg_iteration"] = round(ms / u * 1e3, 2)
+    _, _, n_local_items = ctx.local_size("items")
 
     out = {
         "metric": METRIC,
@@ -753,30 +821,33 @@ def main():
                    "cg_scalars": ("peer all-reduce (IPC)" if getattr(ctx, "peer_scalars", False)
                                   else "rccl all-reduce" if dist is not None else "local"),
                    "cg_iteration": "one pass" if onepass else "matvec + update"},
-        "roofline": {"kernel": cls, "bound": bound, "achieved": round(achieved, 2),
-                     "peak": peak, "unit": unit, "frac": round(achieved / peak, 4),
-                     "traffic": traffic,
-                     "alg_bytes_per_launch": int(nbytes), "alg_flops_per_launch": int(nflops),
-                     "avg_launch_us": round(avg_s * 1e6, 2), "gather": gather,
-                     "units_per_launch": round(units_per_launch, 3)},
+    }
+    if args.full:
+        out["roofline"], kernel_table = kernel_report(st, ctx, args, k, world, c5, onepass,
+                                                      n_local_users)
+    out.update({
         "iteration_roofline": iteration_roofline(k, value),
         "cg_iterations": {"users_total": st["cg_users_total"],
                           "items_total": st["cg_items_total"],
                           "per_step_users": st["cg_users_total"] / args.steps,
                           "per_step_items": st["cg_items_total"] / args.steps},
-        "cg_rate": gpu_cg_rate(st, n_local_users, n_local_items),
-        "kernels": kernel_table,
-        "phase_ms_per_step": {p: round(v / args.steps, 3) for p, v in st["phase_ms"].items()},
         "timing": ("timed region without per-launch events; kernel table and roofline from "
                    "an event-instrumented replay of the same steps" if replay else
                    "one event-instrumented timed region" if instrument else
                    "timed region without per-launch events (no kernel table)"),
-        "ms_per_step_with_kernel_events": round(events_ms, 3) if events_ms else None,
-        "replay_cg_identical": replay_identical,
-        "same_window": same_window,
-        "trajectory": trajectory,
-    }
-    if dist is not None:
+    })
+    if args.full:
+        out.update({
+            "cg_rate": gpu_cg_rate(st, n_local_users, n_local_items),
+            "kernels": kernel_table,
+            "phase_ms_per_step": {p: round(v / args.steps, 3)
+                                  for p, v in st["phase_ms"].items()},
+            "ms_per_step_with_kernel_events": round(events_ms, 3) if events_ms else None,
+            "replay_cg_identical": replay_identical,
+            "same_window": same_window,
+            "trajectory": trajectory,
+        })
+    if args.full and dist is not None:
         out["decomposition"] = step_decomposition(st, args.steps, elapsed, ctx, k, world, dist,
                                                   events_ms)
     if shards is not None:
@@ -807,7 +878,7 @@ def main():
                                    / cr["ms_per_cg_iteration_users"], 1),
                     "items": round(cb["cg"]["ms_per_cg_iteration_items"]
                                    / cr["ms_per_cg_iteration_items"], 1)}
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     ctx.close()
     if rank == 0:

@@ -16,7 +16,7 @@ from conftest import ROOT
 
 BENCH = os.path.join(ROOT, "bench.py")
 SMALL = ["--shape", "ml-full", "--scale", "0.125", "--k", "64", "--steps", "3", "--warmup", "2",
-         "--no-cpu"]
+         "--full", "--no-cpu"]
 
 
 def run_bench(args, timeout=600, env=None):
@@ -34,6 +34,62 @@ def test_world_size_mismatch_is_refused():
     r = run_bench(["--gpus", "4"], timeout=120, env={"WORLD_SIZE": "2", "RANK": "0",
                                                        "LOCAL_RANK": "0"})
     assert r.returncode == 2 and r.stdout == ""
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 tables; beyond the byte budget a fixed,
+    seeded sample of rows, the same from call to call (CPU: a stand-in
+    context)."""
+    import numpy as np
+    import bench
+
+    class Ctx:
+        num_users, num_items, k = 700, 300, 7
+
+        def get_factors(self):
+            rng = np.random.RandomState(3)
+            return rng.uniform(-1, 1, 700 * 8), rng.uniform(-1, 1, 300 * 7)
+
+    bench.dump_outputs(str(tmp_path / "a"), Ctx())
+    U, V = np.load(tmp_path / "a" / "U.npy"), np.load(tmp_path / "a" / "V.npy")
+    Uf, Vf = Ctx().get_factors()
+    assert U.dtype == V.dtype == np.float32 and U.shape == (700, 8) and V.shape == (300, 7)
+    assert np.array_equal(U, Uf.reshape(700, 8).astype(np.float32))
+    assert np.array_equal(V, Vf.reshape(300, 7).astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 10_000)
+    bench.dump_outputs(str(tmp_path / "b"), Ctx())
+    bench.dump_outputs(str(tmp_path / "c"), Ctx())
+    Ub, Vb = np.load(tmp_path / "b" / "U.npy"), np.load(tmp_path / "b" / "V.npy")
+    assert Ub.nbytes + Vb.nbytes <= 10_000 and 0 < Ub.shape[0] < 700 and 0 < Vb.shape[0] < 300
+    assert np.array_equal(Ub, np.load(tmp_path / "c" / "U.npy"))
+    assert np.array_equal(Vb, np.load(tmp_path / "c" / "V.npy"))
+    rows = {r.tobytes() for r in U}
+    assert all(r.tobytes() in rows for r in Ub)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(gpu, tmp_path):
+    """Without --full the line carries the headline fields only, --steps sets
+    the timed steps, and --dump-outputs leaves the last step's factors."""
+    import numpy as np
+    plain = [a for a in SMALL if a not in ("--full", "--no-cpu")]
+    r = run_bench(["--gpus", "1", "--dump-outputs", str(tmp_path)] + plain)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    a = json.loads(lines[0])
+    assert a["steps"] == 3 and a["warmup"] == 2 and a["unit"] == "ratings/s"
+    assert a["higher_is_better"] is True and a["dtype"] == "f32+f64"
+    assert a["ms_per_step"] > 0
+    assert a["value"] == pytest.approx(a["config"]["n_ratings"] / (a["ms_per_step"] / 1e3),
+                                       rel=1e-3)
+    for key in ("roofline", "kernels", "cpu_baseline", "same_window", "trajectory"):
+        assert key not in a
+    U, V = np.load(tmp_path / "U.npy"), np.load(tmp_path / "V.npy")
+    k = a["config"]["k"]
+    assert U.dtype == V.dtype == np.float32
+    assert U.shape == (a["config"]["users"], k + 1) and V.shape == (a["config"]["items"], k)
+    assert np.isfinite(U).all() and np.isfinite(V).all() and np.abs(V).max() > 0
 
 
 @pytest.mark.gpu

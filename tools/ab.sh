@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 n=0
 for v in $ORDER; do
   n=$((n+1))
-  MR_LIB_PATH=$PWD/var_libs/$v/cpp_ls_lib.so timeout -k 10 300 python -u bench.py --no-cpu "$@" > $OUT/${n}_$v.json 2> $OUT/${n}_$v.err
+  MR_LIB_PATH=$PWD/var_libs/$v/cpp_ls_lib.so timeout -k 10 300 python -u bench.py --full --no-cpu "$@" > $OUT/${n}_$v.json 2> $OUT/${n}_$v.err
   rc=$?; if [ $rc -ne 0 ]; then echo "$v rc=$rc: stop"; tail -5 $OUT/${n}_$v.err; exit $rc; fi
   python3 -c "
 import json,sys; d=json.load(open('$OUT/${n}_$v.json'))

@@ -21,7 +21,7 @@ fi
 rc=$?
 grep -E "FAILED|ERROR" $OUT/tests.log | head -40; tail -2 $OUT/tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "TESTS rc=$rc: stop"; exit $rc; fi
-timeout -k 10 600 python -u bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python -u bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 rc=$?
 cat $OUT/bench.json; tail -3 $OUT/bench.err
 exit $rc
