@@ -53,6 +53,7 @@ enum {
   MR_K_CG_RES_ITEMS,     /* resident CG solve, item side                      */
   MR_K_EXCHANGE,         /* sharded: factor all-gather of a half-step (pack,
                             collective, unstage)                             */
+  MR_K_REGULARIZE,       /* ridge pass on a side's normal equations (lambda > 0) */
   MR_K_COUNT
 };
 
@@ -169,6 +170,34 @@ int mr_als_get_factors(mr_als* ctx, double* U, double* V);
 int mr_als_init_factors(mr_als* ctx, unsigned long long seed);
 
 int mr_als_set_solver(mr_als* ctx, int solver, double ridge);
+/* Regularisation of both half-steps: after every Gram, G_e += lambda w_e I_k
+ * on the k factor coordinates of every local entity, w_e = 1
+ * (MR_REG_CONSTANT) or the entity's rating count (MR_REG_WEIGHTED, "ALS-WR").
+ * The user bias is never penalised.  lambda = 0 (the default) issues no
+ * launch and leaves every path as it is.  With lambda > 0 the CG solver takes
+ * the unfused start whatever MR_OPT_FUSE_START says (the fused start works on
+ * the unregularised accumulators); the Cholesky solver gets the regularised
+ * G, and its own `ridge` (mr_als_set_solver: constant, bias included) still
+ * adds on top.  In a sharded run every rank must set the same lambda and mode:
+ * they decide which launches are issued.  -1 on a NULL context, a negative or
+ * non-finite lambda or an unknown mode. */
+enum { MR_REG_CONSTANT = 0, MR_REG_WEIGHTED = 1 };
+int mr_als_set_regularization(mr_als* ctx, double lambda, int mode);
+/* The pieces of the regularised objective at the current factors, computed on
+ * the device in fp64: out = {sse, n, pen_users, pen_items} with
+ *   sse = sum over the user view of (r - u[:k].v - u[k])^2, n its ratings,
+ *   pen_users = sum_u w_u |u[:k]|^2, pen_items = sum_i w_i |v_i|^2
+ * over this context's own users / items, w as the current mode weighs them;
+ * lambda is not multiplied in: J = sse + lambda (pen_users + pen_items).  A
+ * shard returns its local sums (add them over ranks).  Deferred solves of
+ * mr_als_iterate are drained before the tables are read.  Two calls on the
+ * same state return the same bits. */
+int mr_als_objective(mr_als* ctx, double out[4]);
+/* Held-out error on the device: out = {sum (r - prediction)^2, n} for n
+ * (user, item, rating) triples.  An id outside the tables fails the call
+ * (-1, mr_last_error) and leaves the context usable. */
+int mr_als_sse(mr_als* ctx, long long n, const int* user_ids, const int* item_ids,
+               const double* ratings, double out[2]);
 /* Timing of every kernel launch with HIP events (off by default). */
 int mr_als_set_timing(mr_als* ctx, int enable);
 /* Engine options (mr_als_set_option; in a sharded run every rank must set

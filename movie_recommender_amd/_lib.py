@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MR_LIB_PATH") or os.path.join(HERE, "lib", "cpp_ls_li
 
 K_NAMES = ["gram_users", "gram_items", "slab_reduce", "matvec_users",
            "matvec_items", "cg_update", "cg_control", "solve", "cg_start_split",
-           "resident_users", "resident_items", "exchange"]
+           "resident_users", "resident_items", "exchange", "regularize"]
 
 
 class MrStats(ctypes.Structure):
@@ -136,6 +136,9 @@ SIGNATURES = {
     "mr_als_set_factors": (ctypes.c_int, [VP, DP, DP]),
     "mr_als_get_factors": (ctypes.c_int, [VP, DP, DP]),
     "mr_als_set_solver": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_double]),
+    "mr_als_set_regularization": (ctypes.c_int, [VP, ctypes.c_double, ctypes.c_int]),
+    "mr_als_objective": (ctypes.c_int, [VP, DP]),
+    "mr_als_sse": (ctypes.c_int, [VP, ctypes.c_longlong, IP, IP, DP, DP]),
     "mr_als_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
     "mr_als_set_option": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_double]),
     "mr_set_gram_chunk": (ctypes.c_int, [ctypes.c_int]),

@@ -7,6 +7,7 @@
 // leave a message in mr_last_error() (also printed to stderr).
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -281,6 +282,28 @@ int mr_als_set_solver(mr_als* ctx, int solver, double ridge) {
   return 0;
 }
 
+int mr_als_set_regularization(mr_als* ctx, double lambda, int mode) {
+  MR_CHECK(ctx, "null context");
+  MR_CHECK(std::isfinite(lambda) && lambda >= 0.0, "lambda must be finite and >= 0");
+  MR_CHECK(mode == MR_REG_CONSTANT || mode == MR_REG_WEIGHTED, "unknown regularization mode");
+  ctx->eng.reg_lambda = lambda;
+  ctx->eng.reg_mode = mode;
+  return 0;
+}
+
+int mr_als_objective(mr_als* ctx, double out[4]) {
+  MR_CHECK(ctx, "null context");
+  MR_CHECK(out, "null argument");
+  return guarded([&]() { return ctx->eng.objective(out); });
+}
+
+int mr_als_sse(mr_als* ctx, long long n, const int* user_ids, const int* item_ids,
+               const double* ratings, double out[2]) {
+  MR_CHECK(ctx, "null context");
+  MR_CHECK(out && (n == 0 || (user_ids && item_ids && ratings)), "null argument");
+  return guarded([&]() { return ctx->eng.sse(n, user_ids, item_ids, ratings, out); });
+}
+
 int mr_als_set_timing(mr_als* ctx, int enable) {
   MR_CHECK(ctx, "null context");
   ctx->eng.timing = enable != 0;
@@ -364,7 +387,8 @@ int mr_als_build_normal_equations(mr_als* ctx, int side) {
   MR_CHECK(side == MR_SIDE_USERS || side == MR_SIDE_ITEMS, "unknown side");
   return guarded([&]() -> int {
     MR_HIP(hipSetDevice(ctx->eng.device));
-    if (ctx->eng.gram(side == MR_SIDE_USERS ? ctx->eng.su : ctx->eng.si)) return -1;
+    mr::Side& S = side == MR_SIDE_USERS ? ctx->eng.su : ctx->eng.si;
+    if (ctx->eng.gram(S) || ctx->eng.regularize(S)) return -1;
     if (ctx->eng.resolve_timing()) return -1;
     MR_HIP(hipStreamSynchronize(ctx->eng.stream));
     return 0;

@@ -95,6 +95,10 @@ struct Engine {
   int solver = MR_SOLVER_CG;
   double ridge = 0.0;
   int chunk = 2048;
+  // ridge on the k factor coordinates of both sides (mr_als_set_regularization):
+  // G_e += reg_lambda w_e I_k after every Gram, w_e = 1 or the rating count
+  double reg_lambda = 0.0;
+  int reg_mode = MR_REG_WEIGHTED;
   bool fuse_start = true;   // CG start in the Gram epilogue (MR_OPT_FUSE_START)
   bool onepass = true;      // one kernel per CG iteration (MR_OPT_CG_ONEPASS)
   bool resident = true;     // one-pass solves as one resident launch (MR_OPT_CG_RESIDENT)
@@ -174,6 +178,12 @@ struct Engine {
   GramDst direct_dst(Side& S);
   GramDst slab_dst(Side& S);
   int gram(Side& S, bool start = false);
+  // the ridge pass on the side's freshly built G (nothing for reg_lambda = 0)
+  int regularize(Side& S);
+  // {sse, n, pen_users, pen_items} of the current factors (local to a shard)
+  int objective(double* out4);
+  // {sum (r - pred)^2, n} of n host triples
+  int sse(int64_t n, const int* uid, const int* iid, const double* r, double* out2);
   int x_ptrs(Side& S, float** xf, float** xb);
   int cg(Side& S, double min_dec, int max_it, double* final_rr, bool started = false,
          Inflight* deferred = nullptr);

@@ -978,6 +978,17 @@ int Engine::gram(Side& S, bool start) {
   return 0;
 }
 
+// Ridge pass (regularize.hip) over the side's local entities: S.G and S.off
+// are both indexed by local entity, so a shard's e0 needs no offset here.
+int Engine::regularize(Side& S) {
+  if (!(reg_lambda > 0.0)) return 0;
+  hipEvent_t a = nullptr;
+  if (tic(MR_K_REGULARIZE, -1, &a)) return -1;
+  if (launch_ridge_diag(stream, S.E, k, reg_lambda, reg_mode == MR_REG_WEIGHTED, S.off, S.G))
+    return -1;
+  return toc(MR_K_REGULARIZE, -1, a);
+}
+
 int Engine::x_ptrs(Side& S, float** xf, float** xb) {
   if (S.user) {
     *xf = Ufac + S.e0 * ldk;
@@ -1331,8 +1342,11 @@ int Engine::half_step(bool user, double min_dec, int max_it, double* final_rr) {
   }
   const size_t g0 = pending.size();
   // the CG start rides on the MFMA Gram's accumulators (32 <= k <= 128)
-  const bool fused = solver == MR_SOLVER_CG && fuse_start && k >= kMfmaMinK && k <= kMaxK;
-  if (gram(S, fused)) return -1;
+  // (not with a ridge: the fused start forms r0 and q0 from the unregularised
+  // accumulators, so a regularised solve takes the unfused start)
+  const bool fused = solver == MR_SOLVER_CG && fuse_start && k >= kMfmaMinK && k <= kMaxK &&
+                     !(reg_lambda > 0.0);
+  if (gram(S, fused) || regularize(S)) return -1;
   const size_t c0 = pending.size();
   int its = 0;
   double rr = 0.0;
@@ -1449,6 +1463,65 @@ int Engine::predict(int64_t n, const int* uid, const int* iid, double* out) {
   MR_HIP(hipStreamSynchronize(stream));
   dfree(du, stream); dfree(di, stream); dfree(dout, stream);
   return 0;
+}
+
+// The regularised objective's pieces from the current fp32 tables: training
+// SSE and rating count over the user-view CSR (the users' Gram work list),
+// and the penalties sum w_e |x_e|^2 of this context's own users and items
+// (weights as the ridge pass takes them).  Local to a shard.
+int Engine::objective(double* out4) {
+  if (drain()) return -1;
+  MR_HIP(hipSetDevice(device));
+  const bool weighted = reg_mode == MR_REG_WEIGHTED;
+  const int64_t nb_obj = objective_blocks(su.n_work);
+  const int64_t nb_u = row_blocks(su.E, ldk), nb_i = row_blocks(si.E, ldk);
+  double *part = nullptr, *dout = nullptr;
+  int rc = dalloc(&part, 2 * nb_obj + nb_u + nb_i, stream) || dalloc(&dout, 4, stream);
+  if (!rc)
+    rc = launch_objective(stream, su.work, su.n_work, su.idx, su.val, Ufac + su.e0 * ldk,
+                          Ubias + su.e0, Vfac, ldk, part, dout);
+  if (!rc)
+    rc = launch_penalty(stream, su.E, Ufac + su.e0 * ldk, ldk, weighted, su.off,
+                        part + 2 * nb_obj, dout + 2);
+  if (!rc)
+    rc = launch_penalty(stream, si.E, Vfac + si.e0 * ldk, ldk, weighted, si.off,
+                        part + 2 * nb_obj + nb_u, dout + 3);
+  if (!rc) rc = t_stager.d2h(stream, out4, dout, 4 * sizeof(double));
+  dfree(part, stream); dfree(dout, stream);
+  return rc ? -1 : 0;
+}
+
+// Held-out squared error of n host triples on the device; ids are checked
+// against the tables first, as in predict().
+int Engine::sse(int64_t n, const int* uid, const int* iid, const double* r, double* out2) {
+  if (drain()) return -1;
+  MR_CHECK(n >= 0, "sse: negative count");
+  MR_HIP(hipSetDevice(device));
+  out2[0] = 0.0;
+  out2[1] = (double)n;
+  if (n == 0) return 0;
+  const int64_t nblk = row_blocks(n, ldk);
+  int *du = nullptr, *di = nullptr;
+  double *dr = nullptr, *part = nullptr;
+  int rc = dalloc(&du, n, stream) || dalloc(&di, n, stream) || dalloc(&dr, n, stream) ||
+           dalloc(&part, nblk + 1, stream);
+  int flags[2] = {0, 0};
+  if (!rc) rc = t_stager.h2d(stream, du, uid, n * 4) || t_stager.h2d(stream, di, iid, n * 4) ||
+                t_stager.h2d(stream, dr, r, n * 8);
+  if (!rc && hipMemsetAsync(d_flag, 0, 8, stream) != hipSuccess) {
+    set_error("sse: hipMemsetAsync failed");
+    rc = -1;
+  }
+  if (!rc) rc = launch_validate_ids(stream, n, du, 0, (int32_t)U, d_flag) ||
+                launch_validate_ids(stream, n, di, 0, (int32_t)I, d_flag + 1);
+  if (!rc) rc = t_stager.d2h(stream, flags, d_flag, 8);
+  const bool bad = !rc && (flags[0] || flags[1]);
+  if (!rc && !bad)
+    rc = launch_sse(stream, n, du, di, dr, Ufac, Ubias, Vfac, ldk, part, part + nblk) ||
+         t_stager.d2h(stream, out2, part + nblk, sizeof(double));
+  dfree(du, stream); dfree(di, stream); dfree(dr, stream); dfree(part, stream);
+  MR_CHECK(!bad, "sse: id out of range");
+  return rc ? -1 : 0;
 }
 
 int Engine::get_normal_equations(bool user, int n, const int* ents, double* G, double* c) {

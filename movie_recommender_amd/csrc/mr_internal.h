@@ -435,6 +435,28 @@ int launch_gather_f64(hipStream_t s, int64_t n, const int32_t* pos, const double
 int launch_validate_ids(hipStream_t s, int64_t n, const int32_t* ids, int32_t lo,
                         int32_t hi, int* bad);
 
+// Regularised ALS (regularize.hip) ------------------------------------------
+// G_e += lambda w_e I_k on the k factor coordinates of E tri16 blocks (w_e = 1,
+// or off[e+1] - off[e] when weighted); each diagonal entry rounded once.
+int launch_ridge_diag(hipStream_t s, int64_t E, int k, double lambda, bool weighted,
+                      const int64_t* off, float* G);
+// Partial-sum blocks of launch_objective (2 doubles each) and of the per-row
+// kernels launch_penalty / launch_sse (1 double each).
+int64_t objective_blocks(int64_t n_work);
+int64_t row_blocks(int64_t rows, int ldk);
+// out2 = {sum (r - u.v - b_u)^2, ratings visited} over the users' work list
+// (Uloc / Ubloc: the side's local rows of the user table, V: the item table).
+int launch_objective(hipStream_t s, const WorkItem* work, int64_t n_work, const int32_t* idx,
+                     const float* val, const float* Uloc, const float* Ubloc, const float* V,
+                     int ldk, double* part, double* out2);
+// out1 = sum_e w_e |x_e|^2 over E rows of X (w_e as in launch_ridge_diag).
+int launch_penalty(hipStream_t s, int64_t E, const float* X, int ldk, bool weighted,
+                   const int64_t* off, double* part, double* out1);
+// out1 = sum (r - u.v - b_u)^2 over n triples with ids inside the tables.
+int launch_sse(hipStream_t s, int64_t n, const int32_t* uid, const int32_t* iid, const double* r,
+               const float* U, const float* Ub, const float* V, int ldk, double* part,
+               double* out1);
+
 // CSR construction (csr_build.hip) ------------------------------------------
 // Stable sort of n (key, other, value) triples by key - key_base, which must
 // lie in [0, E).  Produces off[E+1] (int64), idx[n] = other, val[n] (as TV).

@@ -260,7 +260,11 @@ def sharded_context(user_ids, item_ids, ratings, k, num_users, num_items, device
     or a ``TorchComm`` (host-staged callbacks carrying the same padded
     exchange buffers; works with gloo).  ``bounds=(ub, ib)`` imposes the
     shard boundaries (default: cost-balanced).  ``scalars="peer"``: the CG
-    scalars go through the peer all-reduce (``attach_peer_scalars``)."""
+    scalars go through the peer all-reduce (``attach_peer_scalars``).
+    Further keywords go to ``AlsContext`` on every rank -- ``reg`` /
+    ``reg_mode`` among them, which must be the same on all ranks; a shard's
+    ``objective()`` is local: sum ``sse``, ``n`` and the penalties over ranks
+    before forming J."""
     import torch.distributed as dist
     from .engine import AlsContext
     rank, world = dist.get_rank(), dist.get_world_size()

@@ -15,6 +15,18 @@ SOLVERS = {"cg": 0, "cholesky": 1}
 OPTIONS = {"fuse_start": 0, "cg_speculate": 1, "wait_timeout_s": 2,
            "cg_onepass": 3, "gram_rhs_mfma": 4, "cg_sweep": 5,
            "peer_timeout_s": 6, "cg_tile_nt": 7, "cg_resident": 8}   # include/mr_als.h
+REG_MODES = {"constant": 0, "weighted": 1}   # MR_REG_* of include/mr_als.h
+
+
+def check_regularization(lam, mode):
+    """(lambda as float, MR_REG_* code); ``ValueError`` for a negative or
+    non-finite lambda or an unknown mode name.  No native call."""
+    if mode not in REG_MODES:
+        raise ValueError(f"reg_mode must be one of {sorted(REG_MODES)}, not {mode!r}")
+    lam = float(lam)
+    if not np.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"reg must be finite and >= 0, not {lam!r}")
+    return lam, REG_MODES[mode]
 
 
 def _i32(a):
@@ -32,11 +44,14 @@ class AlsContext:
     (rating minus movie median), ``k`` item factors (users carry k+1).
     For a shard, pass ``user_range``/``item_range`` and the two rating views
     (``item_view=(uid, iid, r)`` holding every rating of the shard's items).
+    ``reg`` > 0 regularises both half-steps (``set_regularization``).
     """
 
     def __init__(self, user_ids, item_ids, ratings, k, num_users, num_items,
                  device=0, solver="cg", ridge=0.0, timing=False,
-                 user_range=None, item_range=None, item_view=None, gram_chunk=None):
+                 user_range=None, item_range=None, item_view=None, gram_chunk=None,
+                 reg=0.0, reg_mode="weighted"):
+        check_regularization(reg, reg_mode)
         L = _lib.lib()
         self.device = int(device)
         self.k = int(k)
@@ -70,6 +85,9 @@ class AlsContext:
         self._h = h
         self._comm = None
         self.set_solver(solver, ridge)
+        self.reg, self.reg_mode = 0.0, "weighted"   # the engine's defaults
+        if (float(reg), reg_mode) != (self.reg, self.reg_mode):
+            self.set_regularization(reg, reg_mode)
         if timing:
             self.set_timing(True)
 
@@ -95,6 +113,17 @@ class AlsContext:
     def set_solver(self, solver="cg", ridge=0.0):
         _lib.check(_lib.lib().mr_als_set_solver(self._h, SOLVERS[solver], float(ridge)),
                    "mr_als_set_solver")
+
+    def set_regularization(self, lam, mode="weighted"):
+        """Ridge on the k factor coordinates of both sides, ``G_e += lam w_e
+        I_k`` after every Gram: ``mode="constant"`` w_e = 1, ``"weighted"``
+        w_e = the entity's rating count (ALS-WR).  The user bias is never
+        penalised.  ``lam = 0`` is the unregularised engine.  Every rank of a
+        sharded run must set the same values."""
+        lam, code = check_regularization(lam, mode)
+        _lib.check(_lib.lib().mr_als_set_regularization(self._h, lam, code),
+                   "mr_als_set_regularization")
+        self.reg, self.reg_mode = lam, mode
 
     def set_option(self, name, value):
         """Engine option (``mr_als_set_option``): ``fuse_start``,
@@ -244,6 +273,38 @@ class AlsContext:
     @property
     def num_ratings(self):
         return int(_lib.lib().mr_als_num_ratings(self._h))
+
+    def objective(self):
+        """The regularised objective at the current factors, summed on the
+        device in fp64: ``sse`` (training squared error over the user view),
+        ``n`` (its ratings), ``pen_users`` / ``pen_items`` (sum of w_e |x_e|^2
+        over this context's own entities, bias excluded), ``lam`` and
+        ``J = sse + lam (pen_users + pen_items)``.  A shard returns its local
+        sums: add ``sse``, ``n`` and the penalties over ranks."""
+        out = np.empty(4)
+        _lib.check(_lib.lib().mr_als_objective(self._h, out.ctypes.data_as(_lib.DP)),
+                   "mr_als_objective")
+        sse, n, pu, pi = (float(x) for x in out)
+        return {"sse": sse, "n": int(n), "pen_users": pu, "pen_items": pi, "lam": self.reg,
+                "J": sse + self.reg * (pu + pi)}
+
+    def sse(self, user_ids, item_ids, ratings):
+        """(sum of squared errors, n) of the given (user, item, rating)
+        triples, reduced on the device: a held-out error without shipping n
+        predictions back."""
+        uid, iid, r = _i32(user_ids), _i32(item_ids), _f64(ratings)
+        if not len(uid) == len(iid) == len(r):
+            raise ValueError("user_ids, item_ids and ratings differ in length")
+        out = np.empty(2)
+        _lib.check(_lib.lib().mr_als_sse(self._h, len(r), uid.ctypes.data_as(_lib.IP),
+                                         iid.ctypes.data_as(_lib.IP), r.ctypes.data_as(_lib.DP),
+                                         out.ctypes.data_as(_lib.DP)), "mr_als_sse")
+        return float(out[0]), int(out[1])
+
+    def rmse(self, user_ids, item_ids, ratings):
+        """Root mean squared error of the given triples (``sse``)."""
+        s, n = self.sse(user_ids, item_ids, ratings)
+        return float(np.sqrt(s / n)) if n else 0.0
 
     def predict(self, user_ids, item_ids):
         uid, iid = _i32(user_ids), _i32(item_ids)

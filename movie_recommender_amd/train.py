@@ -18,6 +18,8 @@ import os
 import pickle
 import time
 
+import numpy as np
+
 from . import cpp_ls
 
 
@@ -59,4 +61,50 @@ def als_train(factors_list, als_dir, thread_count=None, algorithm=1, verbose=Tru
         _dump(als_dir, f"als{factor}_user_factors", user_factors)
         _dump(als_dir, f"als{factor}_item_factors", item_factors)
         out[factor] = (user_factors, item_factors, iterations)
+    return out
+
+
+def als_train_regularized(factors_list, als_dir, reg, reg_mode="weighted", solver="cholesky",
+                          max_iterations=30, tol=1e-4, verbose=True):
+    """Trains one regularised ALS model per factor on the device-resident
+    engine: ``reg`` is lambda, ``reg_mode`` ``"weighted"`` (penalty lambda n_e
+    |x_e|^2, ALS-WR) or ``"constant"``; the user bias is not penalised.
+
+    Reads and writes the files of ``als_train``.  U0 then V0 are drawn from
+    NumPy's global RNG in ``cpp_ls.als``'s order; ALS iterations run until the
+    relative decrease of the objective J = SSE + lambda (penalties) falls
+    below ``tol`` or ``max_iterations`` is reached.  Returns ``{k: (user_factors,
+    item_factors, iterations, [J after every iteration])}``."""
+    from .engine import AlsContext, check_regularization
+    check_regularization(reg, reg_mode)
+    out = {}
+    for factor in factors_list:
+        num_items = len(_load(als_dir, f"als{factor}_movie_ids"))
+        num_users = len(_load(als_dir, f"als{factor}_user_ids"))
+        user_ids_train, item_ids_train, ratings_train = _load(
+            als_dir, f"als{factor}_user_ratings_train")
+        if verbose:
+            print(_current_time(), "Building regularised ALS factor", factor, "model")
+        user_factors = np.random.uniform(-1, 1, num_users * (factor + 1))
+        item_factors = np.random.uniform(-1, 1, num_items * factor)
+        history = []
+        with AlsContext(user_ids_train, item_ids_train, ratings_train, factor, num_users,
+                        num_items, solver=solver, reg=reg, reg_mode=reg_mode) as ctx:
+            ctx.set_factors(user_factors, item_factors)
+            iterations = 0
+            while iterations < max_iterations:
+                ctx.iterate(1)
+                iterations += 1
+                history.append(ctx.objective()["J"])
+                if verbose:
+                    print(_current_time(), "iteration", iterations, "J =", history[-1])
+                if len(history) > 1 and history[-2] - history[-1] < tol * abs(history[-2]):
+                    break
+            user_factors, item_factors = ctx.get_factors()
+        if verbose:
+            print(_current_time(), "ALS took", iterations, "iterations.",
+                  'Saving "user_factors" and "item_factors" to disk')
+        _dump(als_dir, f"als{factor}_user_factors", user_factors)
+        _dump(als_dir, f"als{factor}_item_factors", item_factors)
+        out[factor] = (user_factors, item_factors, iterations, history)
     return out
