@@ -38,7 +38,10 @@ typedef struct mr_als mr_als;
 enum { MR_SOLVER_CG = 0, MR_SOLVER_CHOLESKY = 1 };
 enum { MR_SIDE_USERS = 0, MR_SIDE_ITEMS = 1 };
 
-/* Kernel classes timed with HIP events when timing is enabled. */
+/* Kernel classes timed with HIP events when timing is enabled.
+ * Implicit-feedback mode (mr_als_set_implicit) adds no class: its weighted
+ * normal-equation kernel is booked as the side's Gram (MR_K_GRAM_*), the
+ * global Gram S and the add pass with the ridge pass (MR_K_REGULARIZE). */
 enum {
   MR_K_GRAM_USERS = 0,   /* normal equations, user side (MFMA gather-Gram)   */
   MR_K_GRAM_ITEMS,       /* normal equations, item side                       */
@@ -183,6 +186,24 @@ int mr_als_set_solver(mr_als* ctx, int solver, double ridge);
  * non-finite lambda or an unknown mode. */
 enum { MR_REG_CONSTANT = 0, MR_REG_WEIGHTED = 1 };
 int mr_als_set_regularization(mr_als* ctx, double lambda, int mode);
+/* alpha > 0: implicit-feedback mode (confidence 1 + alpha r, preference 1 for
+ * stored pairs, 0 for all others; user bias pinned to 0); alpha = 0: off.
+ * The model is Hu, Koren and Volinsky's: the loss runs over ALL (user, item)
+ * pairs, sum c_ui (p_ui - x_u . y_i)^2 + lambda (penalties as
+ * mr_als_set_regularization weighs them), and each half-step solves
+ *   G_e = S + sum_j alpha r_ej y_j y_j^T (+ ridge),  c_e = sum_j (1 + alpha r_ej) y_j
+ * with S the Gram of the whole opposite table.  An entity without ratings gets
+ * the zero vector (the explicit engine keeps its old factors).  Switching the
+ * mode on zeroes the user bias column; while it is on, mr_als_set_factors
+ * stores that column as zero, mr_als_init_factors leaves it zero, and both
+ * solvers return it as exactly zero.  The
+ * CG solver takes the unfused start, as with lambda > 0.  mr_als_objective
+ * then returns {J_data, n, pen_users, pen_items}, J_data the loss over all
+ * pairs.  With alpha = 0 (the default) every launch is the explicit engine's.
+ * -1, leaving the context as it was, on a NULL context, a negative or
+ * non-finite alpha, a sharded context, k > 128, or a stored rating < 0 (checked
+ * on the device when the mode is first switched on). */
+int mr_als_set_implicit(mr_als* ctx, double alpha);
 /* The pieces of the regularised objective at the current factors, computed on
  * the device in fp64: out = {sse, n, pen_users, pen_items} with
  *   sse = sum over the user view of (r - u[:k].v - u[k])^2, n its ratings,

@@ -137,6 +137,7 @@ SIGNATURES = {
     "mr_als_get_factors": (ctypes.c_int, [VP, DP, DP]),
     "mr_als_set_solver": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_double]),
     "mr_als_set_regularization": (ctypes.c_int, [VP, ctypes.c_double, ctypes.c_int]),
+    "mr_als_set_implicit": (ctypes.c_int, [VP, ctypes.c_double]),
     "mr_als_objective": (ctypes.c_int, [VP, DP]),
     "mr_als_sse": (ctypes.c_int, [VP, ctypes.c_longlong, IP, IP, DP, DP]),
     "mr_als_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),

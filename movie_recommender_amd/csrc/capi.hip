@@ -260,9 +260,14 @@ int mr_als_init_factors(mr_als* ctx, unsigned long long seed) {
   return guarded([&]() -> int {
     mr::Engine& E = ctx->eng;
     MR_HIP(hipSetDevice(E.device));
+    const bool implicit = E.implicit_alpha > 0.0;
+    if (implicit && E.drain()) return -1;
     if (mr::launch_init_factors(E.stream, E.U, E.k, E.ldk, seed, 0, E.Ufac, E.Ubias) ||
         mr::launch_init_factors(E.stream, E.I, E.k, E.ldk, seed, 1, E.Vfac, nullptr))
       return -1;
+    // implicit mode: the bias column stays zero (the factor values are the
+    // explicit mode's for the same seed)
+    if (implicit) MR_HIP(hipMemsetAsync(E.Ubias, 0, (E.U + 1) * 4, E.stream));
     MR_HIP(hipStreamSynchronize(E.stream));
     return 0;
   });
@@ -289,6 +294,11 @@ int mr_als_set_regularization(mr_als* ctx, double lambda, int mode) {
   ctx->eng.reg_lambda = lambda;
   ctx->eng.reg_mode = mode;
   return 0;
+}
+
+int mr_als_set_implicit(mr_als* ctx, double alpha) {
+  MR_CHECK(ctx, "mr_als_set_implicit: null context");
+  return guarded([&]() { return ctx->eng.set_implicit(alpha); });
 }
 
 int mr_als_objective(mr_als* ctx, double out[4]) {
@@ -388,7 +398,7 @@ int mr_als_build_normal_equations(mr_als* ctx, int side) {
   return guarded([&]() -> int {
     MR_HIP(hipSetDevice(ctx->eng.device));
     mr::Side& S = side == MR_SIDE_USERS ? ctx->eng.su : ctx->eng.si;
-    if (ctx->eng.gram(S) || ctx->eng.regularize(S)) return -1;
+    if (ctx->eng.normal_equations(S)) return -1;
     if (ctx->eng.resolve_timing()) return -1;
     MR_HIP(hipStreamSynchronize(ctx->eng.stream));
     return 0;

@@ -99,6 +99,13 @@ struct Engine {
   // G_e += reg_lambda w_e I_k after every Gram, w_e = 1 or the rating count
   double reg_lambda = 0.0;
   int reg_mode = MR_REG_WEIGHTED;
+  // implicit-feedback mode (mr_als_set_implicit; implicit.hip): alpha > 0 builds
+  // G_e = S + sum alpha r y y^T, c_e = sum (1 + alpha r) y and pins the user
+  // bias at zero; 0: the explicit engine
+  double implicit_alpha = 0.0;
+  bool implicit_checked = false;   // the stored ratings were found >= 0
+  float* S16 = nullptr;            // tri16 S = Y^T Y of the current half-step
+  float* yty_part = nullptr;       // its per-wave partials
   bool fuse_start = true;   // CG start in the Gram epilogue (MR_OPT_FUSE_START)
   bool onepass = true;      // one kernel per CG iteration (MR_OPT_CG_ONEPASS)
   bool resident = true;     // one-pass solves as one resident launch (MR_OPT_CG_RESIDENT)
@@ -178,6 +185,12 @@ struct Engine {
   GramDst direct_dst(Side& S);
   GramDst slab_dst(Side& S);
   int gram(Side& S, bool start = false);
+  int set_implicit(double alpha);
+  // the implicit mode's normal equations of a side, up to the ridge pass
+  int gram_implicit(Side& S);
+  // a side's normal equations as the current mode builds them, ridge included
+  int normal_equations(Side& S, bool start = false);
+  int objective_implicit(double* out4);
   // the ridge pass on the side's freshly built G (nothing for reg_lambda = 0)
   int regularize(Side& S);
   // {sse, n, pen_users, pen_items} of the current factors (local to a shard)

@@ -76,6 +76,7 @@ Engine::~Engine() {
     }
     dfree(d_state, stream); dfree(partials, stream); dfree(d_flag, stream); dfree(xbins, stream);
     dfree(d_resgen, stream); dfree(d_resctl, stream);
+    dfree(S16, stream); dfree(yty_part, stream);
     dfree(d_peer, stream);
     for (void* q : peer_opened) (void)hipIpcCloseMemHandle(q);
     if (peer_buf) (void)hipFree(peer_buf);
@@ -502,6 +503,8 @@ int Engine::set_factors(const double* hU, const double* hV) {
   if (hU && U) {
     memcpy(h_fac, hU, nU * 8);
     rc |= launch_unpack_factors(stream, U, k + 1, k, ldk, h_fac, Ufac, Ubias);
+    // implicit mode: the bias column is stored as zero
+    if (implicit_alpha > 0.0) MR_HIP(hipMemsetAsync(Ubias, 0, (U + 1) * 4, stream));
   }
   if (hV && I) {
     memcpy(h_fac + nU, hV, nV * 8);
@@ -978,6 +981,70 @@ int Engine::gram(Side& S, bool start) {
   return 0;
 }
 
+// Implicit-feedback mode (implicit.hip).  Switching it on checks the stored
+// ratings once (all >= 0), allocates S and its partials and zeroes the user
+// bias; every refusal leaves the context as it was.
+int Engine::set_implicit(double alpha) {
+  MR_CHECK(std::isfinite(alpha) && alpha >= 0.0, "implicit: alpha must be finite and >= 0");
+  if (drain()) return -1;
+  if (alpha == 0.0) {
+    implicit_alpha = 0.0;
+    return 0;
+  }
+  MR_CHECK(!sharded() && su.E == U && si.E == I, "implicit: sharded contexts are not supported");
+  MR_CHECK(k <= kMaxK, "implicit: k must be <= 128");
+  MR_HIP(hipSetDevice(device));
+  if (!implicit_checked) {
+    int bad = 0;
+    MR_HIP(hipMemsetAsync(d_flag, 0, 4, stream));
+    if (launch_any_negative(stream, su.nnz, su.val, d_flag)) return -1;
+    MR_D2H(&bad, d_flag, 4, stream);
+    MR_HIP(hipStreamSynchronize(stream));
+    MR_CHECK(!bad, "implicit: a stored rating is negative (or not a number)");
+    implicit_checked = true;
+  }
+  if (!S16 && dalloc(&S16, gsize_of(k), stream)) return -1;
+  if (!yty_part &&
+      dalloc(&yty_part, (int64_t)yty_parts(std::max(U, I)) * gsize_of(k), stream))
+    return -1;
+  MR_HIP(hipMemsetAsync(Ubias, 0, (U + 1) * 4, stream));
+  MR_HIP(hipStreamSynchronize(stream));
+  implicit_alpha = alpha;
+  return 0;
+}
+
+// Implicit normal equations of a side: the weighted kernel in the Gram's
+// place (booked as the side's Gram), slab_reduce as it stands, then S of the
+// opposite table and the add pass (booked with the ridge pass, MR_K_REGULARIZE).
+int Engine::gram_implicit(Side& S) {
+  const bool user = S.user;
+  const float* F = user ? Vfac : Ufac;
+  const int64_t rows = user ? I : U;
+  hipEvent_t a = nullptr;
+  const int cls = user ? MR_K_GRAM_USERS : MR_K_GRAM_ITEMS;
+  if (tic(cls, -1, &a)) return -1;
+  if (launch_wnormal(stream, user, k, S.work, S.n_work, S.idx, S.val, (float)implicit_alpha, F,
+                     (int)rows, direct_dst(S), slab_dst(S)))
+    return -1;
+  if (toc(cls, -1, a)) return -1;
+  if (S.n_split) {
+    if (tic(MR_K_SLAB_REDUCE, -1, &a)) return -1;
+    if (launch_slab_reduce(stream, user, k, S.split, S.n_split, S.slab, S.rec, direct_dst(S)))
+      return -1;
+    if (toc(MR_K_SLAB_REDUCE, -1, a)) return -1;
+  }
+  if (tic(MR_K_REGULARIZE, -1, &a)) return -1;
+  if (launch_yty16(stream, k, F, rows, yty_part, S16) ||
+      launch_add_s(stream, S.E, k, S16, S.G, S.Gs, S.Gn, S.Cb))
+    return -1;
+  return toc(MR_K_REGULARIZE, -1, a);
+}
+
+int Engine::normal_equations(Side& S, bool start) {
+  if (implicit_alpha > 0.0) return gram_implicit(S) || regularize(S) ? -1 : 0;
+  return gram(S, start) || regularize(S) ? -1 : 0;
+}
+
 // Ridge pass (regularize.hip) over the side's local entities: S.G and S.off
 // are both indexed by local entity, so a shard's e0 needs no offset here.
 int Engine::regularize(Side& S) {
@@ -1345,8 +1412,8 @@ int Engine::half_step(bool user, double min_dec, int max_it, double* final_rr) {
   // (not with a ridge: the fused start forms r0 and q0 from the unregularised
   // accumulators, so a regularised solve takes the unfused start)
   const bool fused = solver == MR_SOLVER_CG && fuse_start && k >= kMfmaMinK && k <= kMaxK &&
-                     !(reg_lambda > 0.0);
-  if (gram(S, fused) || regularize(S)) return -1;
+                     !(reg_lambda > 0.0) && !(implicit_alpha > 0.0);
+  if (normal_equations(S, fused)) return -1;
   const size_t c0 = pending.size();
   int its = 0;
   double rr = 0.0;
@@ -1472,6 +1539,7 @@ int Engine::predict(int64_t n, const int* uid, const int* iid, double* out) {
 int Engine::objective(double* out4) {
   if (drain()) return -1;
   MR_HIP(hipSetDevice(device));
+  if (implicit_alpha > 0.0) return objective_implicit(out4);
   const bool weighted = reg_mode == MR_REG_WEIGHTED;
   const int64_t nb_obj = objective_blocks(su.n_work);
   const int64_t nb_u = row_blocks(su.E, ldk), nb_i = row_blocks(si.E, ldk);
@@ -1489,6 +1557,39 @@ int Engine::objective(double* out4) {
   if (!rc) rc = t_stager.d2h(stream, out4, dout, 4 * sizeof(double));
   dfree(part, stream); dfree(dout, stream);
   return rc ? -1 : 0;
+}
+
+// Implicit mode: out4[0] is the loss over ALL (user, item) pairs,
+//   sum_u x_u^T S x_u + sum over stored pairs of (1 + w)(1 - d)^2 - d^2,
+// S = V^T V in fp64; n and the penalties as above.
+int Engine::objective_implicit(double* out4) {
+  const bool weighted = reg_mode == MR_REG_WEIGHTED;
+  const int64_t nb_obj = objective_blocks(su.n_work);
+  const int64_t nb_u = row_blocks(su.E, ldk), nb_i = row_blocks(si.E, ldk);
+  const int64_t n_xsx = yty64_blocks(I) * ldk * ldk + nb_u;
+  double *part = nullptr, *dout = nullptr, *S64 = nullptr;
+  int rc = dalloc(&part, 2 * nb_obj + nb_u + nb_i + n_xsx, stream) || dalloc(&dout, 5, stream) ||
+           dalloc(&S64, (int64_t)ldk * ldk, stream);
+  if (!rc)
+    rc = launch_implicit_obs(stream, su.work, su.n_work, su.idx, su.val, implicit_alpha, Ufac,
+                             Vfac, ldk, part, dout);
+  if (!rc)
+    rc = launch_penalty(stream, su.E, Ufac, ldk, weighted, su.off, part + 2 * nb_obj, dout + 2);
+  if (!rc)
+    rc = launch_penalty(stream, si.E, Vfac, ldk, weighted, si.off, part + 2 * nb_obj + nb_u,
+                        dout + 3);
+  if (!rc)
+    rc = launch_xsx(stream, k, Vfac, I, su.E, Ufac, part + 2 * nb_obj + nb_u + nb_i, S64,
+                    dout + 4);
+  double h[5] = {0, 0, 0, 0, 0};
+  if (!rc) rc = t_stager.d2h(stream, h, dout, 5 * sizeof(double));
+  dfree(part, stream); dfree(dout, stream); dfree(S64, stream);
+  if (rc) return -1;
+  out4[0] = h[4] + h[0];
+  out4[1] = h[1];
+  out4[2] = h[2];
+  out4[3] = h[3];
+  return 0;
 }
 
 // Held-out squared error of n host triples on the device; ids are checked

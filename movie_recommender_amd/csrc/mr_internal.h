@@ -457,6 +457,39 @@ int launch_sse(hipStream_t s, int64_t n, const int32_t* uid, const int32_t* iid,
                const float* U, const float* Ub, const float* V, int ldk, double* part,
                double* out1);
 
+// out[c] = sum over blocks b < nblk of part[nc b + c], in block order.
+int launch_sum_partials(hipStream_t s, const double* part, int64_t nblk, int nc, double* out);
+
+// Implicit-feedback ALS (implicit.hip), k <= 128 ------------------------------
+// Weighted normal equations over a side's Gram work list: sum w y y^T (tri16)
+// and sum (1 + w) y, w = fl32(alpha val), into the explicit Gram's
+// destinations (the user side's Gs / Cb / Gn are written as zero).  F: the
+// opposite table, row zrow all zero.
+int launch_wnormal(hipStream_t s, bool user_side, int k, const WorkItem* work, int64_t n_work,
+                   const int32_t* idx, const float* val, float alpha, const float* F, int zrow,
+                   GramDst direct, GramDst slab);
+// S16 = F^T F over all `rows` rows of F (row `rows` all zero), packed in tri16
+// (gsize_of(k) floats); part: yty_parts(rows) x gsize_of(k) floats.  Fixed
+// partial order, combined in fp64: the same table gives the same bits.
+int yty_parts(int64_t rows);
+int launch_yty16(hipStream_t s, int k, const float* F, int64_t rows, float* part, float* S16);
+// G_e += S16 for E tri16 blocks; Gs != nullptr (user side): Gs_e = 0, Gn_e = 1,
+// Cb_e = 0 for every entity.
+int launch_add_s(hipStream_t s, int64_t E, int k, const float* S16, float* G, float* Gs,
+                 float* Gn, float* Cb);
+// *flag = 1 if any of n values is negative or not a number.
+int launch_any_negative(hipStream_t s, int64_t n, const float* val, int* flag);
+// out2 = {sum over stored pairs of (1 + alpha r)(1 - d)^2 - d^2, pairs}, d =
+// u . v, over the users' work list; part: 2 objective_blocks(n_work) doubles.
+int launch_implicit_obs(hipStream_t s, const WorkItem* work, int64_t n_work, const int32_t* idx,
+                        const float* val, double alpha, const float* Uloc, const float* V,
+                        int ldk, double* part, double* out2);
+// out1 = sum over E rows x of X of x^T (Y^T Y) x in fp64, Y: `rows` rows.
+// part: yty64_blocks(rows) ldk^2 + row_blocks(E, ldk) doubles; S64: ldk^2.
+int64_t yty64_blocks(int64_t rows);
+int launch_xsx(hipStream_t s, int k, const float* Y, int64_t rows, int64_t E, const float* X,
+               double* part, double* S64, double* out1);
+
 // CSR construction (csr_build.hip) ------------------------------------------
 // Stable sort of n (key, other, value) triples by key - key_base, which must
 // lie in [0, E).  Produces off[E+1] (int64), idx[n] = other, val[n] (as TV).

@@ -29,6 +29,20 @@ def check_regularization(lam, mode):
     return lam, REG_MODES[mode]
 
 
+def check_implicit(alpha):
+    """alpha as float; ``ValueError`` unless it is a finite number >= 0 (0:
+    the mode is off).  No native call."""
+    if isinstance(alpha, (str, bytes)) or alpha is None:
+        raise ValueError(f"implicit_alpha must be a number, not {alpha!r}")
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"implicit_alpha must be a number, not {alpha!r}") from None
+    if not np.isfinite(alpha) or alpha < 0.0:
+        raise ValueError(f"implicit_alpha must be finite and >= 0, not {alpha!r}")
+    return alpha
+
+
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
@@ -45,13 +59,16 @@ class AlsContext:
     For a shard, pass ``user_range``/``item_range`` and the two rating views
     (``item_view=(uid, iid, r)`` holding every rating of the shard's items).
     ``reg`` > 0 regularises both half-steps (``set_regularization``).
+    ``implicit_alpha`` > 0 trains on implicit feedback (``set_implicit``): the
+    ratings are then counts or strengths >= 0.
     """
 
     def __init__(self, user_ids, item_ids, ratings, k, num_users, num_items,
                  device=0, solver="cg", ridge=0.0, timing=False,
                  user_range=None, item_range=None, item_view=None, gram_chunk=None,
-                 reg=0.0, reg_mode="weighted"):
+                 reg=0.0, reg_mode="weighted", implicit_alpha=0.0):
         check_regularization(reg, reg_mode)
+        implicit_alpha = check_implicit(implicit_alpha)
         L = _lib.lib()
         self.device = int(device)
         self.k = int(k)
@@ -88,6 +105,13 @@ class AlsContext:
         self.reg, self.reg_mode = 0.0, "weighted"   # the engine's defaults
         if (float(reg), reg_mode) != (self.reg, self.reg_mode):
             self.set_regularization(reg, reg_mode)
+        self.implicit_alpha = 0.0
+        if implicit_alpha > 0.0:
+            try:
+                self.set_implicit(implicit_alpha)
+            except Exception:
+                self.close()
+                raise
         if timing:
             self.set_timing(True)
 
@@ -125,6 +149,17 @@ class AlsContext:
                    "mr_als_set_regularization")
         self.reg, self.reg_mode = lam, mode
 
+    def set_implicit(self, alpha):
+        """Implicit-feedback mode (Hu, Koren, Volinsky): ``alpha > 0`` gives a
+        stored pair the confidence ``1 + alpha r`` and preference 1, every other
+        pair confidence 1 and preference 0; the user bias is pinned to zero.
+        ``alpha = 0`` switches back to the explicit engine.  ``RuntimeError``
+        (the context stays usable) for a sharded context, ``k > 128`` or a
+        negative stored rating."""
+        alpha = check_implicit(alpha)
+        _lib.check(_lib.lib().mr_als_set_implicit(self._h, alpha), "mr_als_set_implicit")
+        self.implicit_alpha = alpha
+
     def set_option(self, name, value):
         """Engine option (``mr_als_set_option``): ``fuse_start``,
         ``cg_speculate`` (0/1) or ``wait_timeout_s``."""
@@ -154,7 +189,8 @@ class AlsContext:
                    "mr_als_set_factors")
 
     def init_factors(self, seed=0):
-        """Seeded uniform(-1, 1) factors generated on the device."""
+        """Seeded uniform(-1, 1) factors generated on the device (implicit
+        mode: the bias column stays zero)."""
         _lib.check(_lib.lib().mr_als_init_factors(self._h, int(seed)), "mr_als_init_factors")
 
     def get_factors(self):
@@ -280,7 +316,9 @@ class AlsContext:
         ``n`` (its ratings), ``pen_users`` / ``pen_items`` (sum of w_e |x_e|^2
         over this context's own entities, bias excluded), ``lam`` and
         ``J = sse + lam (pen_users + pen_items)``.  A shard returns its local
-        sums: add ``sse``, ``n`` and the penalties over ranks."""
+        sums: add ``sse``, ``n`` and the penalties over ranks.  In implicit
+        mode ``sse`` holds the data term of the loss over ALL (user, item)
+        pairs, ``sum c_ui (p_ui - x_u . y_i)^2``."""
         out = np.empty(4)
         _lib.check(_lib.lib().mr_als_objective(self._h, out.ctypes.data_as(_lib.DP)),
                    "mr_als_objective")
