@@ -16,6 +16,10 @@
  *                       per half-step over the block-diagonal A^T A with the
  *                       reference's scalars and stop rules (matrix.cpp:456-529)
  *   MR_SOLVER_CHOLESKY  exact per-entity solve (G_e + ridge I) x_e = c_e
+ *   MR_SOLVER_NNLS      exact per-entity non-negative solve: minimise
+ *                       1/2 x^T (G_e + ridge I) x - c_e^T x subject to x >= 0 on
+ *                       the k factor coordinates (the user bias stays free), by
+ *                       block principal pivoting (mr_als_set_nnls)
  *
  * Sharding (multi-GPU, one process per GPU): a context may own a contiguous
  * range of users and of items (mr_als_create_shard); factor tables stay
@@ -35,7 +39,7 @@ extern "C" {
 
 typedef struct mr_als mr_als;
 
-enum { MR_SOLVER_CG = 0, MR_SOLVER_CHOLESKY = 1 };
+enum { MR_SOLVER_CG = 0, MR_SOLVER_CHOLESKY = 1, MR_SOLVER_NNLS = 2 };
 enum { MR_SIDE_USERS = 0, MR_SIDE_ITEMS = 1 };
 
 /* Kernel classes timed with HIP events when timing is enabled.
@@ -50,7 +54,7 @@ enum {
   MR_K_MATVEC_ITEMS,     /* CG batched block GEMV, item side                  */
   MR_K_CG_UPDATE,        /* CG x/r update + r.r partials (both sides)         */
   MR_K_CG_CONTROL,       /* CG scalar reduction / stop rule (both sides)      */
-  MR_K_SOLVE,            /* batched Cholesky (exact mode)                      */
+  MR_K_SOLVE,            /* batched Cholesky (exact mode) or NNLS solve        */
   MR_K_CG_START,         /* CG start of split entities (fused start)          */
   MR_K_CG_RES_USERS,     /* resident CG solve (all iterations), user side     */
   MR_K_CG_RES_ITEMS,     /* resident CG solve, item side                      */
@@ -172,7 +176,33 @@ int mr_als_get_factors(mr_als* ctx, double* U, double* V);
  * stream).  For workloads whose host tables would be multi-GB (C5). */
 int mr_als_init_factors(mr_als* ctx, unsigned long long seed);
 
+/* MR_SOLVER_NNLS is refused (-1, context unchanged) on a sharded context; like
+ * the Cholesky solver it needs k <= 128 (a half-step with a larger k fails). */
 int mr_als_set_solver(mr_als* ctx, int solver, double ridge);
+/* The non-negative solver (MR_SOLVER_NNLS): per local entity, Kim and Park's
+ * block principal pivoting with their backup rule on the side's normal
+ * equations as last built (Gram, + S in implicit mode, + lambda ridge, + the
+ * solver's own ridge on every diagonal entry).  A round solves G_FF x_F = c_F
+ * on the free set F (plus the user bias, which is never constrained) by
+ * Cholesky in fp64, forms y = G x - c on the rest, and exchanges the
+ * coordinates with x_j < 0 or y_j < 0; none left: converged.
+ *   max_rounds   cap on the rounds per entity; 0: the default 4 (k + 1);
+ *                negative: -1.  At the cap the last x is stored with its
+ *                negative constrained coordinates set to 0 and the entity counts
+ *                as unconverged.
+ *   warm_start   non-zero (default): F starts as the coordinates whose
+ *                previous x is > 0; 0: F starts empty.
+ * A block that is not positive definite (a diagonal entry or a pivot <= 0)
+ * keeps its previous x with the constrained coordinates clamped at 0 and is
+ * counted in nonpd_users / nonpd_items.  Coordinates held at zero are stored
+ * as +0. */
+int mr_als_set_nnls(mr_als* ctx, int max_rounds, int warm_start);
+/* The side's LAST NNLS solve: out = {entities, sum of rounds, max rounds,
+ * unconverged entities}; -1 if the side has no NNLS solve yet. */
+int mr_als_nnls_stats(mr_als* ctx, int side, long long out[4]);
+/* Its per-entity rounds (E entries, mr_als_local_size): r > 0 converged in r
+ * rounds, -r stopped unconverged at the cap r, 0 not positive definite. */
+int mr_als_nnls_rounds(mr_als* ctx, int side, int* rounds);
 /* Regularisation of both half-steps: after every Gram, G_e += lambda w_e I_k
  * on the k factor coordinates of every local entity, w_e = 1
  * (MR_REG_CONSTANT) or the entity's rating count (MR_REG_WEIGHTED, "ALS-WR").

@@ -280,11 +280,37 @@ int mr_als_get_factors(mr_als* ctx, double* U, double* V) {
 
 int mr_als_set_solver(mr_als* ctx, int solver, double ridge) {
   MR_CHECK(ctx, "null context");
-  MR_CHECK(solver == MR_SOLVER_CG || solver == MR_SOLVER_CHOLESKY, "unknown solver");
+  MR_CHECK(solver == MR_SOLVER_CG || solver == MR_SOLVER_CHOLESKY || solver == MR_SOLVER_NNLS,
+           "unknown solver");
   MR_CHECK(ridge >= 0.0, "ridge must be >= 0");
-  ctx->eng.solver = solver;
-  ctx->eng.ridge = ridge;
+  mr::Engine& E = ctx->eng;
+  MR_CHECK(solver != MR_SOLVER_NNLS || (!E.sharded() && E.su.E == E.U && E.si.E == E.I),
+           "mr_als_set_solver: the NNLS solver does not support sharded contexts");
+  E.solver = solver;
+  E.ridge = ridge;
   return 0;
+}
+
+int mr_als_set_nnls(mr_als* ctx, int max_rounds, int warm_start) {
+  MR_CHECK(ctx, "mr_als_set_nnls: null context");
+  MR_CHECK(max_rounds >= 0, "mr_als_set_nnls: max_rounds must be >= 0 (0: the default)");
+  ctx->eng.nnls_max_rounds = max_rounds;
+  ctx->eng.nnls_warm = warm_start != 0;
+  return 0;
+}
+
+int mr_als_nnls_stats(mr_als* ctx, int side, long long out[4]) {
+  MR_CHECK(ctx, "mr_als_nnls_stats: null context");
+  MR_CHECK(out, "mr_als_nnls_stats: null argument");
+  MR_CHECK(side == MR_SIDE_USERS || side == MR_SIDE_ITEMS, "mr_als_nnls_stats: unknown side");
+  return guarded([&]() { return ctx->eng.nnls_report(side == MR_SIDE_USERS, nullptr, out); });
+}
+
+int mr_als_nnls_rounds(mr_als* ctx, int side, int* rounds) {
+  MR_CHECK(ctx, "mr_als_nnls_rounds: null context");
+  MR_CHECK(rounds, "mr_als_nnls_rounds: null argument");
+  MR_CHECK(side == MR_SIDE_USERS || side == MR_SIDE_ITEMS, "mr_als_nnls_rounds: unknown side");
+  return guarded([&]() { return ctx->eng.nnls_report(side == MR_SIDE_USERS, rounds, nullptr); });
 }
 
 int mr_als_set_regularization(mr_als* ctx, double lambda, int mode) {

@@ -33,6 +33,8 @@ struct Side {
                                // cache policy: [0] plain loads, [1] non-temporal
   int n_part_rs[2] = {0, 0};   // resident CG solve grid (0: not available)
   double* start_parts = nullptr;   // fused CG start: (r.r, p.Gp) per block
+  int* nnls_rounds = nullptr;      // NNLS solver: rounds per entity of the last solve [E]
+  bool nnls_solved = false;        // nnls_rounds holds a solve
   int64_t n_start_pairs = 0;
 };
 
@@ -94,6 +96,9 @@ struct Engine {
   int cur_parts = 1;
   int solver = MR_SOLVER_CG;
   double ridge = 0.0;
+  // MR_SOLVER_NNLS (mr_als_set_nnls; nnls.hip): round cap (0: 4 (k + 1)) and start
+  int nnls_max_rounds = 0;
+  bool nnls_warm = true;
   int chunk = 2048;
   // ridge on the k factor coordinates of both sides (mr_als_set_regularization):
   // G_e += reg_lambda w_e I_k after every Gram, w_e = 1 or the rating count
@@ -208,6 +213,10 @@ struct Engine {
                  Inflight* deferred = nullptr);
   CgStart cg_start_of(Side& S);
   int solve(Side& S);
+  int solve_nnls(Side& S);
+  // the side's last NNLS solve: per-entity rounds (rounds may be NULL) and
+  // {entities, sum of rounds, max rounds, unconverged} (out4 may be NULL)
+  int nnls_report(bool user, int* rounds, long long* out4);
   int half_step(bool user, double min_dec, int max_it, double* final_rr);
   // read back the deferred solves until at most `keep` remain in flight:
   // their CG counts into the stats, errors reported here

@@ -62,6 +62,7 @@ static void free_side(Side& S, hipStream_t s) {
   dfree(S.r, s); dfree(S.p, s); dfree(S.q, s);
   dfree(S.rb, s); dfree(S.pb, s); dfree(S.qb, s);
   dfree(S.start_parts, s);
+  dfree(S.nnls_rounds, s);
 }
 
 Engine::~Engine() {
@@ -1378,6 +1379,7 @@ int Engine::cg_onepass(Side& S, double min_dec, int max_it, double* final_rr, bo
 }
 
 int Engine::solve(Side& S) {
+  if (solver == MR_SOLVER_NNLS) return solve_nnls(S);
   float *xf, *xb;
   x_ptrs(S, &xf, &xb);
   MR_HIP(hipMemsetAsync(d_flag, 0, 4, stream));
@@ -1392,6 +1394,56 @@ int Engine::solve(Side& S) {
   MR_HIP(hipStreamSynchronize(stream));
   if (S.user) stats.nonpd_users += bad;
   else stats.nonpd_items += bad;
+  return 0;
+}
+
+// The non-negative solver in the Cholesky solver's place (nnls.hip): same
+// operands, same timing class; the per-entity rounds stay on the device until
+// nnls_report is asked for them.
+int Engine::solve_nnls(Side& S) {
+  MR_CHECK(!sharded(), "nnls: sharded contexts are not supported");
+  float *xf, *xb;
+  x_ptrs(S, &xf, &xb);
+  if (!S.nnls_rounds && dalloc(&S.nnls_rounds, S.E, stream)) return -1;
+  MR_HIP(hipMemsetAsync(d_flag, 0, 4, stream));
+  const int cap = nnls_max_rounds > 0 ? nnls_max_rounds : 4 * (k + 1);
+  hipEvent_t a = nullptr;
+  if (tic(MR_K_SOLVE, -1, &a)) return -1;
+  if (launch_nnls(stream, S.user, S.E, k, ridge, cap, nnls_warm, S.G, S.Gs, S.Gn, S.C, S.Cb, xf,
+                  xb, S.nnls_rounds, d_flag))
+    return -1;
+  if (toc(MR_K_SOLVE, -1, a)) return -1;
+  int bad = 0;
+  MR_D2H(&bad, d_flag, 4, stream);
+  MR_HIP(hipStreamSynchronize(stream));
+  S.nnls_solved = true;
+  if (S.user) stats.nonpd_users += bad;
+  else stats.nonpd_items += bad;
+  return 0;
+}
+
+int Engine::nnls_report(bool user, int* rounds, long long* out4) {
+  if (drain()) return -1;
+  MR_HIP(hipSetDevice(device));
+  Side& S = user ? su : si;
+  MR_CHECK(S.nnls_solved, "nnls: this side has no NNLS solve yet");
+  std::vector<int> h(S.E);
+  if (S.E > 0) MR_D2H(h.data(), S.nnls_rounds, S.E * 4, stream);
+  MR_HIP(hipStreamSynchronize(stream));
+  if (rounds) std::copy(h.begin(), h.end(), rounds);
+  if (out4) {
+    long long sum = 0, mx = 0, unconv = 0;
+    for (int r : h) {
+      const long long a = r < 0 ? -(long long)r : r;
+      sum += a;
+      mx = std::max(mx, a);
+      unconv += r < 0;
+    }
+    out4[0] = S.E;
+    out4[1] = sum;
+    out4[2] = mx;
+    out4[3] = unconv;
+  }
   return 0;
 }
 

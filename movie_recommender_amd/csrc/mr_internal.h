@@ -379,6 +379,12 @@ int launch_solve(hipStream_t s, bool user_side, int64_t E, int k, double ridge,
                  const float* G, const float* Gs, const float* Gn,
                  const float* C, const float* Cb, float* x, float* xb,
                  int* nonpd);
+// nnls.hip: per-entity non-negative solve by block principal pivoting (same
+// operands as launch_solve; rounds[E] gets the rounds used: > 0 converged,
+// < 0 stopped at the cap, 0 not positive definite and counted in *nonpd).
+int launch_nnls(hipStream_t s, bool user_side, int64_t E, int k, double ridge, int max_rounds,
+                bool warm, const float* G, const float* Gs, const float* Gn, const float* C,
+                const float* Cb, float* x, float* xb, int* rounds, int* nonpd);
 int launch_unpack_factors(hipStream_t s, int64_t rows, int width, int k,
                           int ldk, const double* src, float* fac, float* bias);
 int launch_pack_factors(hipStream_t s, int64_t rows, int width, int k, int ldk,

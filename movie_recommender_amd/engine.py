@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-SOLVERS = {"cg": 0, "cholesky": 1}
+SOLVERS = {"cg": 0, "cholesky": 1, "nnls": 2}   # MR_SOLVER_* of include/mr_als.h
 OPTIONS = {"fuse_start": 0, "cg_speculate": 1, "wait_timeout_s": 2,
            "cg_onepass": 3, "gram_rhs_mfma": 4, "cg_sweep": 5,
            "peer_timeout_s": 6, "cg_tile_nt": 7, "cg_resident": 8}   # include/mr_als.h
@@ -135,8 +135,40 @@ class AlsContext:
 
     # -- configuration -------------------------------------------------------
     def set_solver(self, solver="cg", ridge=0.0):
+        """``"cg"`` (the reference's), ``"cholesky"`` (exact per entity) or
+        ``"nnls"`` (exact per entity with the k factor coordinates >= 0 and the
+        user bias free; ``set_nnls``).  ``RuntimeError``, the solver unchanged,
+        for ``"nnls"`` on a sharded context."""
         _lib.check(_lib.lib().mr_als_set_solver(self._h, SOLVERS[solver], float(ridge)),
                    "mr_als_set_solver")
+
+    def set_nnls(self, max_rounds=0, warm_start=True):
+        """Options of the ``"nnls"`` solver (block principal pivoting):
+        ``max_rounds`` caps the rounds per entity (0: the default 4 (k + 1));
+        ``warm_start`` starts each entity's free set from the positive
+        coordinates of its previous factors instead of the empty set."""
+        _lib.check(_lib.lib().mr_als_set_nnls(self._h, int(max_rounds), int(bool(warm_start))),
+                   "mr_als_set_nnls")
+
+    def nnls_stats(self, side):
+        """The side's last NNLS solve: ``entities``, ``rounds_total``,
+        ``rounds_max`` and ``unconverged`` (entities stopped at the cap)."""
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(_lib.lib().mr_als_nnls_stats(self._h, 0 if side in (0, "users") else 1, out),
+                   "mr_als_nnls_stats")
+        return {"entities": int(out[0]), "rounds_total": int(out[1]),
+                "rounds_max": int(out[2]), "unconverged": int(out[3])}
+
+    def nnls_rounds(self, side):
+        """Rounds per local entity of the side's last NNLS solve (int32):
+        r > 0 converged in r rounds, -r stopped at the cap r, 0 not positive
+        definite (the entity kept its previous factors, clamped at 0)."""
+        _, E, _ = self.local_size(side)
+        out = np.empty(E, np.int32)
+        _lib.check(_lib.lib().mr_als_nnls_rounds(self._h, 0 if side in (0, "users") else 1,
+                                                 out.ctypes.data_as(_lib.IP)),
+                   "mr_als_nnls_rounds")
+        return out
 
     def set_regularization(self, lam, mode="weighted"):
         """Ridge on the k factor coordinates of both sides, ``G_e += lam w_e

@@ -24,7 +24,11 @@ def als_implicit(user_ids, item_ids, confidence, k, num_users, num_items, alpha=
     shapes; the bias column is dropped); ALS iterations run until the relative
     decrease of J falls below ``tol`` or ``max_iterations`` is reached.
     Returns ``(X[num_users, k], Y[num_items, k], iterations, [J after every
-    iteration])``; the score of a pair is ``X[u] @ Y[i]``."""
+    iteration])``; the score of a pair is ``X[u] @ Y[i]``.
+
+    ``solver="nnls"`` constrains every factor to be >= 0 (each half-step is
+    the exact non-negative block minimiser, ``AlsContext.set_nnls``): X and Y
+    come back non-negative, so every score is a non-negative affinity."""
     alpha = check_implicit(alpha)
     if not alpha > 0.0:
         raise ValueError("alpha must be > 0")

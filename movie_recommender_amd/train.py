@@ -74,7 +74,12 @@ def als_train_regularized(factors_list, als_dir, reg, reg_mode="weighted", solve
     NumPy's global RNG in ``cpp_ls.als``'s order; ALS iterations run until the
     relative decrease of the objective J = SSE + lambda (penalties) falls
     below ``tol`` or ``max_iterations`` is reached.  Returns ``{k: (user_factors,
-    item_factors, iterations, [J after every iteration])}``."""
+    item_factors, iterations, [J after every iteration])}``.
+
+    ``solver="nnls"`` keeps the k factor coordinates of every user and item
+    >= 0 (the exact non-negative block minimiser per half-step,
+    ``AlsContext.set_nnls``); the user bias (last entry of each user row)
+    stays free and may be negative."""
     from .engine import AlsContext, check_regularization
     check_regularization(reg, reg_mode)
     out = {}
