@@ -258,9 +258,15 @@ __global__ __launch_bounds__(SM_NT) void sim_find_kernel(
     }
     __syncthreads();
     for (int c0 = 0; c0 < SM_RS; c0 += SM_NT) {
-      if (s_nbuf + SM_NT > SM_CAP) {   // block-uniform: keep the T with most reviewers
-        block_sort(cj, cn, cs, s_nbuf, 0);
-        if (tid == 0) s_nbuf = min(s_nbuf, T);
+      // Every thread takes the list length into a register and the barrier
+      // holds this chunk's atomicAdd(&s_nbuf) back until all have read, so
+      // the cut decision is the same value in every wave by construction
+      // (block_sort contains barriers: it must not be entered by some waves).
+      const int held = s_nbuf;
+      __syncthreads();
+      if (held + SM_NT > SM_CAP) {   // keep the T with most reviewers
+        block_sort(cj, cn, cs, held, 0);
+        if (tid == 0) s_nbuf = min(held, T);
         __syncthreads();
       }
       const int jj = c0 + tid, j = base + jj;
