@@ -4,8 +4,9 @@ The shared library exports the reference ABI (``include/cpp_ls_lib.h``), the
 device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_serving.h``), the general sparse least squares
 (``include/mr_cg.h``), the training-set preparation
-(``include/mr_prep.h``) and the similar-movies database
-(``include/mr_similar.h``).  There is no CPU
+(``include/mr_prep.h``), the similar-movies database
+(``include/mr_similar.h``) and the ranking evaluation / implicit fold-in
+(``include/mr_ranking.h``).  There is no CPU
 fallback: if the library is missing or cannot load, every entry point raises.
 """
 import ctypes
@@ -209,6 +210,13 @@ SIGNATURES = {
     "mr_similar_find": (ctypes.c_int, [VP, ctypes.c_int, IP, DP, ctypes.c_int, ctypes.c_int, IP,
                                        DP, IP]),
     "mr_similar_last_ms": (ctypes.c_double, [VP]),
+    # ranking evaluation and implicit fold-in (include/mr_ranking.h)
+    "mr_rank_counts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      DP, DP, DP, DP, LLP, IP, LLP, IP, IP, IP, IP, DP, IP, DP]),
+    "mr_rank_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mr_implicit_fold_in": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_int, LLP, IP, DP, DP, IP]),
     "mr_last_error": (ctypes.c_char_p, []),
     "mr_device_count": (ctypes.c_int, []),
     "mr_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),

@@ -9,10 +9,17 @@ confidence 1".  The loss runs over ALL pairs,
 
 and is never formed densely (``AlsContext.set_implicit``, DESIGN.md "Implicit
 feedback").  There is no user bias in this model.
+
+Behind a trained model (DESIGN.md "Ranking evaluation and implicit fold-in"):
+``fold_in`` solves the user half-step for users that were not in the training
+set, and ``ImplicitModel`` bundles fold-in, ranking evaluation and top-N.
 """
 import numpy as np
 
+from . import _lib
 from .engine import AlsContext, check_implicit, check_regularization
+
+FOLD_IN_MAX_K = 128
 
 
 def als_implicit(user_ids, item_ids, confidence, k, num_users, num_items, alpha=40.0,
@@ -52,3 +59,126 @@ def als_implicit(user_ids, item_ids, confidence, k, num_users, num_items, alpha=
     X = U.reshape(num_users, k + 1)[:, :k].copy()
     Y = V.reshape(num_items, k).copy()
     return X, Y, iterations, history
+
+
+def _lists_csr(item_lists):
+    """(offsets int64[B + 1], items int64[nnz], r f64[nnz]) of ``item_lists``:
+    a sequence of ``[(item, r)]`` lists, or a CSR triple ``(offsets, items,
+    r)`` whose first member is an ndarray."""
+    if isinstance(item_lists, tuple) and len(item_lists) == 3 and \
+            isinstance(item_lists[0], np.ndarray):
+        off = np.ascontiguousarray(item_lists[0], np.int64)
+        items, r = np.asarray(item_lists[1]), np.asarray(item_lists[2], np.float64)
+        if off.ndim != 1 or off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0) or \
+                items.ndim != 1 or off[-1] != len(items) or r.shape != items.shape:
+            raise ValueError("offsets must be int64[B + 1], non-decreasing, from 0 to len(items); "
+                             "items and r 1-D of that length")
+    else:
+        lists = [list(l) for l in item_lists]
+        off = np.zeros(len(lists) + 1, np.int64)
+        off[1:] = np.cumsum([len(l) for l in lists])
+        items = np.array([it for l in lists for it, _ in l])
+        r = np.array([rv for l in lists for _, rv in l], np.float64)
+    if items.size and not np.issubdtype(items.dtype, np.integer):
+        raise ValueError("item ids must be integers")
+    return off, items.astype(np.int64), r
+
+
+def fold_in(Y, item_lists, alpha=40.0, reg=0.01, reg_mode="constant", device=0):
+    """Factors of users that were not in the training set, from the item
+    factors ``Y[I, k]`` (``k <= 128``) of an implicit model: per user, with
+    ``w = alpha r``, the Cholesky solve (fp64) of
+
+        (Y^T Y + sum w y y^T + lambda_u I) x = sum (1 + w) y,
+
+    ``lambda_u = reg`` (``"constant"``) or ``reg`` times the length of the
+    user's list (``"weighted"``) -- ``als_implicit``'s user half-step.
+    ``item_lists`` is a sequence of ``[(item, r)]`` lists (``r >= 0``), or a
+    CSR triple ``(offsets int64[B + 1], items, r)``.  Returns ``(X[B, k],
+    status int32[B])``: status 1 solved, 0 a pivot was not positive (only
+    with ``reg = 0``; the row is zero).  An empty list gives the zero row.
+
+    ``ValueError`` before any native call for a bad ``alpha`` / ``reg`` /
+    ``reg_mode``, ``k`` outside 1..128, factors that are not finite, an item
+    id out of range or an ``r`` that is negative or not finite."""
+    alpha = check_implicit(alpha)
+    reg, mode = check_regularization(reg, reg_mode)
+    Y = np.ascontiguousarray(Y, np.float64)
+    if Y.ndim != 2 or not 1 <= Y.shape[1] <= FOLD_IN_MAX_K:
+        raise ValueError(f"Y must be [items, k] with k in 1..{FOLD_IN_MAX_K}")
+    if not np.all(np.isfinite(Y)):
+        raise ValueError("factors must be finite")
+    n_items, k = Y.shape
+    off, items, r = _lists_csr(item_lists)
+    if items.size and (items.min() < 0 or items.max() >= n_items):
+        raise ValueError("item id out of range")
+    if not np.all(np.isfinite(r)) or np.any(r < 0):
+        raise ValueError("r must be finite and >= 0")
+    B = len(off) - 1
+    X = np.zeros((max(B, 1), k))
+    status = np.zeros(max(B, 1), np.int32)
+    item32 = np.ascontiguousarray(items if items.size else np.zeros(1), np.int32)
+    r = np.ascontiguousarray(r if r.size else np.zeros(1), np.float64)
+    ip, dp = _lib.IP, _lib.DP
+    _lib.check(_lib.lib().mr_implicit_fold_in(
+        int(device), k, n_items, Y.ctypes.data_as(dp), alpha, reg, mode, B,
+        off.ctypes.data_as(_lib.LLP), item32.ctypes.data_as(ip), r.ctypes.data_as(dp),
+        X.ctypes.data_as(dp), status.ctypes.data_as(ip)), "mr_implicit_fold_in")
+    return X[:B], status[:B]
+
+
+class ImplicitModel:
+    """A trained implicit-feedback model ``(X[U, k], Y[I, k])`` with the
+    hyper-parameters it was trained with: fold-in of new users, ranking
+    evaluation and top-N on one GPU.  The score of a pair is ``X[u] @ Y[i]``
+    in the exact order of ``ranking.rank_counts``."""
+
+    def __init__(self, X, Y, alpha=40.0, reg=0.01, reg_mode="constant", device=0):
+        self.alpha = check_implicit(alpha)
+        self.reg, _ = check_regularization(reg, reg_mode)
+        self.reg_mode = reg_mode
+        self.X = np.ascontiguousarray(X, np.float64)
+        self.Y = np.ascontiguousarray(Y, np.float64)
+        if self.X.ndim != 2 or self.Y.ndim != 2 or self.X.shape[1] != self.Y.shape[1]:
+            raise ValueError("X and Y must be 2-D arrays with the same number of factors")
+        self.k = self.Y.shape[1]
+        self.device = int(device)
+        self._table = None
+
+    def fold_in(self, lists):
+        """``fold_in`` with the model's Y, alpha and regularisation."""
+        return fold_in(self.Y, lists, self.alpha, self.reg, self.reg_mode, self.device)
+
+    def rank_eval(self, test, exclude=None, n=10, weights=None):
+        """``ranking.rank_eval`` of the model's own users on held-out pairs."""
+        from .ranking import rank_eval
+        return rank_eval(self.X, self.Y, test, exclude, n, weights, device=self.device)
+
+    def top_n(self, x_rows, rated=None, num_results=10):
+        """Per row of ``x_rows[B, k]`` (trained or folded-in user factors)
+        the first ``num_results`` items by (score, item id) descending that
+        are not in ``rated[u]``: a list of ``[(score, item)]`` per user.  Runs
+        on a ``MovieTable`` with the identity id map, zero medians and a zero
+        bias column; adding 0.0 twice leaves every comparison as it is."""
+        from .serving import MovieTable
+        if self._table is None:
+            n_items = self.Y.shape[0]
+            ids = {i: i for i in range(n_items)}
+            self._table = MovieTable(self.k, self.Y.reshape(-1), ids, dict.fromkeys(ids, 0.0),
+                                     self.device)
+        x = np.atleast_2d(np.asarray(x_rows, np.float64))
+        if x.shape[1] != self.k:
+            raise ValueError("user factor rows must have k entries")
+        xb = np.concatenate([x, np.zeros((x.shape[0], 1))], axis=1)
+        return self._table.top_n(xb, rated, num_results)
+
+    def close(self):
+        if self._table is not None:
+            self._table.close()
+            self._table = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
