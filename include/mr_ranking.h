@@ -69,7 +69,9 @@ int mr_rank_set_tuning(int user_chunk, int item_groups, int lds_pairs);
  *   (MR_REG_WEIGHTED);  x_u = Cholesky solve of G_u x = c_u.
  * x_out: f64[n_users * k].  status (optional): 1 solved, 0 a pivot was not
  * positive (possible only with reg = 0) and the row is all zero.  An empty
- * list gives exactly the zero row with status 1.
+ * list gives exactly the zero row with status 1.  mr_fold_in (mr_foldin.h) is
+ * the general form -- new items, explicit models, non-negative factors -- and
+ * returns these bits with MR_FOLD_IMPLICIT and nonneg = 0.
  *
  * Refused (-1): k outside 1 .. 128, an id out of range, an r that is negative
  * or not finite, a negative or non-finite alpha or reg, an unknown reg_mode,

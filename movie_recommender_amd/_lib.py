@@ -5,8 +5,9 @@ device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_serving.h``), the general sparse least squares
 (``include/mr_cg.h``), the training-set preparation
 (``include/mr_prep.h``), the similar-movies database
-(``include/mr_similar.h``) and the ranking evaluation / implicit fold-in
-(``include/mr_ranking.h``).  There is no CPU
+(``include/mr_similar.h``), the ranking evaluation / implicit fold-in
+(``include/mr_ranking.h``) and the general fold-in
+(``include/mr_foldin.h``).  There is no CPU
 fallback: if the library is missing or cannot load, every entry point raises.
 """
 import ctypes
@@ -217,6 +218,11 @@ SIGNATURES = {
     "mr_implicit_fold_in": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP,
                                            ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                            ctypes.c_int, LLP, IP, DP, DP, IP]),
+    # fold-in for every trained model (include/mr_foldin.h)
+    "mr_fold_in": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP, DP, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, LLP, IP, DP, DP, IP,
+                                  IP]),
     "mr_last_error": (ctypes.c_char_p, []),
     "mr_device_count": (ctypes.c_int, []),
     "mr_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <algorithm>
 #include <cstdlib>
+#include <new>
 #include <string>
 
 namespace mr {
@@ -510,5 +512,91 @@ int build_csr(hipStream_t s, int64_t n, int64_t E, const int32_t* d_key,
 int sort_rows_by_first_col(hipStream_t s, int64_t rows, int64_t cols, const int64_t* rp,
                            const int32_t* ci, const double* v, int32_t* perm, int64_t* rp2,
                            int32_t* ci2, double* v2);
+
+// Handle-free entry points (ranking.hip, foldin.hip) ---------------------------
+template <typename T>
+struct RkBuf {   // call-scoped device buffer
+  T* p = nullptr;
+  RkBuf() = default;
+  RkBuf(const RkBuf&) = delete;
+  RkBuf& operator=(const RkBuf&) = delete;
+  ~RkBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(int64_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    MR_HIP(hipMalloc((void**)&p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
+    return 0;
+  }
+  int upload(const T* h, int64_t n, hipStream_t s) {
+    if (alloc(n)) return -1;
+    if (n > 0) MR_H2D(p, h, n * sizeof(T), s);
+    return 0;
+  }
+  int zeros(int64_t n, hipStream_t s) {
+    if (alloc(n)) return -1;
+    MR_HIP(hipMemsetAsync(p, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(T), s));
+    return 0;
+  }
+};
+
+struct RkScope {   // stream and the two timing events of one call
+  hipStream_t s = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~RkScope() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (s) (void)hipStreamDestroy(s);
+  }
+  int init(int device) {
+    MR_HIP(hipSetDevice(device));
+    MR_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    MR_HIP(hipEventCreate(&ev[0]));
+    MR_HIP(hipEventCreate(&ev[1]));
+    return 0;
+  }
+  template <typename F>
+  int timed(double* ms, F&& launch) {
+    MR_HIP(hipEventRecord(ev[0], s));
+    launch();
+    MR_HIP(hipGetLastError());
+    MR_HIP(hipEventRecord(ev[1], s));
+    MR_HIP(hipEventSynchronize(ev[1]));
+    float t = 0.f;
+    MR_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
+    if (ms) *ms += t;
+    return 0;
+  }
+};
+
+// offsets of a CSR by entity: start at 0, never decrease
+inline bool rk_offsets_ok(const long long* off, int n) {
+  if (off[0] != 0) return false;
+  for (int u = 0; u < n; ++u)
+    if (off[u + 1] < off[u]) return false;
+  return true;
+}
+
+template <typename F>
+int rk_guard(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    set_error("host out of memory");
+  } catch (...) {
+    set_error("unexpected C++ exception");
+  }
+  return -1;
+}
+
+// fp64 S = Y^T Y, natural k x k (ranking.hip K-F1): the partial kernel on a
+// grid of (nblk, ceil(k^2 / (256 FY_NQ))) blocks into part[nblk][k^2], then
+// the combine over k^2 threads.
+constexpr int FY_CH = 16, FY_NQ = 8;
+__global__ void fold_yty_partial_kernel(const double* __restrict__ Y, int64_t rows, int k,
+                                        double* __restrict__ part);
+__global__ void fold_yty_combine_kernel(const double* __restrict__ part, int nblk, int n,
+                                        double* __restrict__ S);
 
 }  // namespace mr

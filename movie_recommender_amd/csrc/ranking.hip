@@ -420,8 +420,6 @@ __global__ __launch_bounds__(256) void rank_exclude_kernel(
 // 2048 g + 2047 of part[b] (thread t owns entries 2048 g + t + 256 q); the
 // combine adds the partials in block order: a fixed order, and S is exactly
 // symmetric (y_i y_j and y_j y_i are the same products in the same order).
-constexpr int FY_CH = 16, FY_NQ = 8;
-
 __global__ __launch_bounds__(256) void fold_yty_partial_kernel(const double* __restrict__ Y,
                                                                int64_t rows, int k,
                                                                double* __restrict__ part) {
@@ -588,70 +586,6 @@ __global__ __launch_bounds__(256) void implicit_fold_in_kernel(
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-template <typename T>
-struct RkBuf {   // call-scoped device buffer
-  T* p = nullptr;
-  RkBuf() = default;
-  RkBuf(const RkBuf&) = delete;
-  RkBuf& operator=(const RkBuf&) = delete;
-  ~RkBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(int64_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    MR_HIP(hipMalloc((void**)&p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
-    return 0;
-  }
-  int upload(const T* h, int64_t n, hipStream_t s) {
-    if (alloc(n)) return -1;
-    if (n > 0) MR_H2D(p, h, n * sizeof(T), s);
-    return 0;
-  }
-  int zeros(int64_t n, hipStream_t s) {
-    if (alloc(n)) return -1;
-    MR_HIP(hipMemsetAsync(p, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(T), s));
-    return 0;
-  }
-};
-
-struct RkScope {   // stream and the two timing events of one call
-  hipStream_t s = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~RkScope() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (s) (void)hipStreamDestroy(s);
-  }
-  int init(int device) {
-    MR_HIP(hipSetDevice(device));
-    MR_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    MR_HIP(hipEventCreate(&ev[0]));
-    MR_HIP(hipEventCreate(&ev[1]));
-    return 0;
-  }
-  template <typename F>
-  int timed(double* ms, F&& launch) {
-    MR_HIP(hipEventRecord(ev[0], s));
-    launch();
-    MR_HIP(hipGetLastError());
-    MR_HIP(hipEventRecord(ev[1], s));
-    MR_HIP(hipEventSynchronize(ev[1]));
-    float t = 0.f;
-    MR_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
-    if (ms) *ms += t;
-    return 0;
-  }
-};
-
-// offsets of a CSR by entity: start at 0, never decrease
-static bool rk_offsets_ok(const long long* off, int n) {
-  if (off[0] != 0) return false;
-  for (int u = 0; u < n; ++u)
-    if (off[u + 1] < off[u]) return false;
-  return true;
-}
-
 // mr_rank_set_tuning: 0 = default
 static int g_user_chunk = 0, g_item_groups = 0, g_lds_pairs = RK_LC;
 
@@ -832,18 +766,6 @@ static int implicit_fold_in(int device, int k, int n_items, const double* Y, dou
   if (status) MR_D2H(status, dstat.p, (size_t)n_users * 4, s);
   MR_HIP(hipStreamSynchronize(s));
   return 0;
-}
-
-template <typename F>
-static int rk_guard(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    set_error("host out of memory");
-  } catch (...) {
-    set_error("unexpected C++ exception");
-  }
-  return -1;
 }
 
 }  // namespace mr

@@ -12,7 +12,8 @@ feedback").  There is no user bias in this model.
 
 Behind a trained model (DESIGN.md "Ranking evaluation and implicit fold-in"):
 ``fold_in`` solves the user half-step for users that were not in the training
-set, and ``ImplicitModel`` bundles fold-in, ranking evaluation and top-N.
+set, and ``ImplicitModel`` bundles fold-in (of users and of items, non-negative
+for a non-negative model), ranking evaluation and top-N.
 """
 import numpy as np
 
@@ -131,9 +132,11 @@ class ImplicitModel:
     """A trained implicit-feedback model ``(X[U, k], Y[I, k])`` with the
     hyper-parameters it was trained with: fold-in of new users, ranking
     evaluation and top-N on one GPU.  The score of a pair is ``X[u] @ Y[i]``
-    in the exact order of ``ranking.rank_counts``."""
+    in the exact order of ``ranking.rank_counts``.  ``nonneg=True`` for a
+    model trained with ``solver="nnls"``: folded-in rows are then the exact
+    non-negative minimisers, like the trained ones."""
 
-    def __init__(self, X, Y, alpha=40.0, reg=0.01, reg_mode="constant", device=0):
+    def __init__(self, X, Y, alpha=40.0, reg=0.01, reg_mode="constant", device=0, nonneg=False):
         self.alpha = check_implicit(alpha)
         self.reg, _ = check_regularization(reg, reg_mode)
         self.reg_mode = reg_mode
@@ -143,11 +146,26 @@ class ImplicitModel:
             raise ValueError("X and Y must be 2-D arrays with the same number of factors")
         self.k = self.Y.shape[1]
         self.device = int(device)
+        self.nonneg = bool(nonneg)
         self._table = None
 
     def fold_in(self, lists):
-        """``fold_in`` with the model's Y, alpha and regularisation."""
+        """``fold_in`` with the model's Y, alpha and regularisation: ``(X[B,
+        k], status)``.  A non-negative model goes through ``foldin.fold_in``
+        (status -1: the solve stopped at its round cap)."""
+        if self.nonneg:
+            from .foldin import fold_in as general
+            return general(self.Y, lists, "implicit", alpha=self.alpha, reg=self.reg,
+                           reg_mode=self.reg_mode, nonneg=True, device=self.device)[:2]
         return fold_in(self.Y, lists, self.alpha, self.reg, self.reg_mode, self.device)
+
+    def fold_in_items(self, lists):
+        """Factors of new items from ``[(user, r)]`` lists (or a CSR triple):
+        the model's item half-step on its user table X.  Returns ``(Y_new[B,
+        k], status)``."""
+        from .foldin import fold_in as general
+        return general(self.X, lists, "implicit", alpha=self.alpha, reg=self.reg,
+                       reg_mode=self.reg_mode, nonneg=self.nonneg, device=self.device)[:2]
 
     def rank_eval(self, test, exclude=None, n=10, weights=None):
         """``ranking.rank_eval`` of the model's own users on held-out pairs."""

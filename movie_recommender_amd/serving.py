@@ -8,7 +8,8 @@ Mirrors:
 * ``get_recommendations`` -- the scoring / sort / exclusion / rotation of
   ``python/app_local/recommend.py:86-115``;
 * ``MovieTable``          -- the device-resident movie side those run on, with
-  batched ``fold_in``, ``scores``, ``top_n`` and ``evaluate``;
+  batched ``fold_in``, ``fold_in_ridge`` (regularised models, no minimum
+  count), ``scores``, ``top_n`` and ``evaluate``;
 * ``als_eval`` and ``compute_ranking_agreement`` (in ``evaluation.py``).
 
 Every score is the reference's fp64 expression evaluated in the reference's
@@ -48,6 +49,7 @@ class MovieTable:
 
     def __init__(self, num_factors, als_movie_factors, als_movie_ids, movie_medians, device=0):
         self.k = int(num_factors)
+        self.device = int(device)
         V = np.ascontiguousarray(als_movie_factors, dtype=np.float64).reshape(-1)
         if V.size % self.k:
             raise ValueError("als_movie_factors length is not a multiple of num_factors")
@@ -133,6 +135,37 @@ class MovieTable:
             X[rows_u] = Xv
             method[rows_u] = mv
         return valid, X, method
+
+    def fold_in_ridge(self, rating_lists, reg, reg_mode="weighted", nonneg=False,
+                      subtract_median=True):
+        """Fold-in for a model trained with ``als_train_regularized``: per
+        user the ridge system of its user half-step (``foldin.fold_in_users``)
+        on ``[(movie_id, rating)]``, the user bias as the unpenalised
+        intercept.  Movie ids map through ``als_movie_ids``; unknown ids are
+        dropped.  With ``subtract_median`` movies without a median are dropped
+        as well and the fit is on ``rating - median`` (what ``scores`` adds
+        back).  There is no minimum count: a user with no usable rating is
+        ``valid = False`` with the zero row.  ``nonneg`` for a model trained
+        with ``solver="nnls"``.  Returns ``(valid bool[B], X f64[B, k+1],
+        status int32[B])``; the rows feed ``scores`` / ``top_n``."""
+        from .foldin import fold_in
+        reg = float(reg)
+        if not reg > 0.0:
+            raise ValueError("fold_in_ridge needs reg > 0")
+        med = np.zeros(self.n_als)
+        if subtract_median:
+            med[self.cand_als] = self.cand_med
+        lists = []
+        for lst in rating_lists:
+            kept = [(self.als_movie_ids[mid], float(r)) for mid, r in lst
+                    if mid in self.als_movie_ids
+                    and (not subtract_median or mid in self.movie_medians)]
+            lists.append(kept)
+        X, status, _ = fold_in(self._V.reshape(self.n_als, self.k), lists, "explicit", True,
+                               med if subtract_median else None, 0.0, reg, reg_mode, nonneg,
+                               device=self.device)
+        valid = np.array([len(l) > 0 for l in lists], bool)
+        return valid, X, status
 
     # -- scoring ------------------------------------------------------------
     def scores(self, X):
