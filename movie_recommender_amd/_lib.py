@@ -6,8 +6,9 @@ device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_cg.h``), the training-set preparation
 (``include/mr_prep.h``), the similar-movies database
 (``include/mr_similar.h``), the ranking evaluation / implicit fold-in
-(``include/mr_ranking.h``) and the general fold-in
-(``include/mr_foldin.h``).  There is no CPU
+(``include/mr_ranking.h``), the general fold-in
+(``include/mr_foldin.h``) and the explanations
+(``include/mr_explain.h``).  There is no CPU
 fallback: if the library is missing or cannot load, every entry point raises.
 """
 import ctypes
@@ -223,6 +224,11 @@ SIGNATURES = {
                                   ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, LLP, IP, DP, DP, IP,
                                   IP]),
+    # explanations (include/mr_explain.h)
+    "mr_explain": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP, DP, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                  ctypes.c_int, LLP, IP, DP, LLP, IP, ctypes.c_int, DP, IP, DP,
+                                  LLP, DP, IP, DP, IP]),
     "mr_last_error": (ctypes.c_char_p, []),
     "mr_device_count": (ctypes.c_int, []),
     "mr_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),

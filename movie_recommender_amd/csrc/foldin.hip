@@ -3,20 +3,9 @@
 // offsets) or implicit (S = T^T T, confidence weights), unconstrained
 // (Cholesky) or non-negative (block principal pivoting).
 // C ABI: include/mr_foldin.h.  DESIGN.md "Fold-in".
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "../../include/mr_als.h"
-#include "../../include/mr_foldin.h"
-#include "mr_internal.h"
+#include "foldin_device.h"
 
 namespace mr {
-
-__device__ __forceinline__ double fi_mul(double a, double b) {   // a product rounded on its own
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 // ---------------------------------------------------------------------------
 // K-FI1: the normal equations of one entity per 256-thread workgroup, the
@@ -31,10 +20,9 @@ __device__ __forceinline__ double fi_mul(double a, double b) {   // a product ro
 //           implicit form every operation and its order are that kernel's, so
 //           the bits are);
 //   !SOLVE: in global memory, block b's slot of `scratch`, for K-FI2.
-// Entity e = e0 + blockIdx.x.
+// Entity e = e0 + blockIdx.x.  The build and the solve are fi_build and
+// fi_cholesky_solve of foldin_device.h, which explain.hip runs as well.
 // ---------------------------------------------------------------------------
-constexpr int FI_NE = 9;
-
 template <bool SOLVE>
 __global__ __launch_bounds__(256) void fold_build_kernel(
     int e0, int k, int icpt, int implicit, int rows_per_stage, double alpha, double reg,
@@ -46,7 +34,6 @@ __global__ __launch_bounds__(256) void fold_build_kernel(
   __shared__ int s_bad;
   const int K = k + icpt;
   const int W = K + 1;    // row width of G: K coordinates, then the rhs
-  const int WS = K + 2;   // row width of the stage: K coordinates, weight, rhs coefficient
   const int e = e0 + blockIdx.x, tid = threadIdx.x;
   const int64_t b = off[e];
   const int M = (int)(off[e + 1] - b);
@@ -60,116 +47,18 @@ __global__ __launch_bounds__(256) void fold_build_kernel(
     }
     return;
   }
-  const int NT = K * (K + 1) / 2;
   double* G = SOLVE ? lds : scratch + (int64_t)blockIdx.x * K * W;   // [K][W]
   double* As = SOLVE ? lds + K * W : lds;                            // [rows_per_stage][WS]
   const double lam = weighted ? reg * (double)M : reg;
-  for (int g0 = 0; g0 < NT; g0 += 256 * FI_NE) {
-    const bool rhs_pass = g0 == 0;
-    int ei[FI_NE], ej[FI_NE];
-    double acc[FI_NE], cacc = 0.0;
-#pragma unroll
-    for (int t = 0; t < FI_NE; ++t) {
-      int f = g0 + tid + 256 * t;
-      acc[t] = 0.0;
-      ei[t] = -1;
-      ej[t] = -1;
-      if (f < NT) {
-        int i = 0, len = K;
-        while (f >= len) {
-          f -= len;
-          ++i;
-          --len;
-        }
-        ei[t] = i;
-        ej[t] = i + f;
-      }
-    }
-    for (int r0 = 0; r0 < M; r0 += rows_per_stage) {
-      const int nr = min(rows_per_stage, M - r0);
-      for (int q = tid; q < nr * WS; q += 256) {
-        const int row = q / WS, j = q % WS;
-        const int64_t p = b + r0 + row;
-        const int id = idx[p];
-        double v;
-        if (j < k) {
-          v = T[(int64_t)id * k + j];
-        } else if (j < K) {
-          v = 1.0;
-        } else if (implicit) {
-          const double w = fi_mul(alpha, r[p]);
-          v = j == K ? w : 1.0 + w;
-        } else {
-          v = j == K ? 1.0 : (roff ? r[p] - roff[id] : r[p]);
-        }
-        As[row * WS + j] = v;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int t = 0; t < FI_NE; ++t) {
-        if (ei[t] < 0) continue;
-        double s = acc[t];
-        for (int row = 0; row < nr; ++row)
-          s = fma(As[row * WS + K] * As[row * WS + ei[t]], As[row * WS + ej[t]], s);
-        acc[t] = s;
-      }
-      if (rhs_pass && tid < K)
-        for (int row = 0; row < nr; ++row)
-          cacc = fma(As[row * WS + K + 1], As[row * WS + tid], cacc);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < FI_NE; ++t) {
-      if (ei[t] < 0) continue;
-      double g = acc[t];
-      if (implicit) g = S[ei[t] * k + ej[t]] + acc[t];
-      if (ei[t] == ej[t] && ei[t] < k) g += lam;
-      G[ei[t] * W + ej[t]] = g;
-      G[ej[t] * W + ei[t]] = g;
-    }
-    if (rhs_pass && tid < K) G[tid * W + K] = cacc;
-  }
+  fi_build(k, icpt, implicit, rows_per_stage, alpha, lam, b, M, idx, r, T, roff, S, G, As);
   if constexpr (SOLVE) {
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    for (int j = 0; j < K; ++j) {
-      if (tid == 0) {
-        const double d = G[j * W + j];
-        if (!(d > 0.0)) s_bad = 1;
-        else G[j * W + j] = sqrt(d);
-      }
-      __syncthreads();
-      if (s_bad) break;
-      const double ljj = G[j * W + j];
-      for (int i = j + 1 + tid; i < K; i += 256) G[i * W + j] /= ljj;
-      __syncthreads();
-      const int m = K - j - 1;
-      for (int q = tid; q < m * m; q += 256) {
-        const int ii = j + 1 + q / m, ll = j + 1 + q % m;
-        if (ll <= ii) G[ii * W + ll] -= G[ii * W + j] * G[ll * W + j];
-      }
-      __syncthreads();
-    }
-    if (s_bad) {   // block-uniform (read after the barrier that follows its last write)
+    if (fi_cholesky_solve(K, G, &s_bad)) {
       for (int i = tid; i < K; i += 256) X[(int64_t)e * K + i] = 0.0;
       if (tid == 0) {
         status[e] = 0;
         rounds[e] = 0;
       }
       return;
-    }
-    // L y = c (right-looking), then L^T x = y
-    for (int p = 0; p < K; ++p) {
-      if (tid == 0) G[p * W + K] /= G[p * W + p];
-      __syncthreads();
-      for (int i = p + 1 + tid; i < K; i += 256) G[i * W + K] -= G[i * W + p] * G[p * W + K];
-      __syncthreads();
-    }
-    for (int p = K - 1; p >= 0; --p) {
-      if (tid == 0) G[p * W + K] /= G[p * W + p];
-      __syncthreads();
-      for (int i = tid; i < p; i += 256) G[i * W + K] -= G[p * W + i] * G[p * W + K];
-      __syncthreads();
     }
     for (int i = tid; i < K; i += 256) X[(int64_t)e * K + i] = G[i * W + K];
     if (tid == 0) {
@@ -343,44 +232,19 @@ __global__ __launch_bounds__(256) void fold_nnls_kernel(
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-static bool all_finite(const double* a, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
-
 static int fold_in(int device, int k, int n_rows, const double* T, const double* row_offset,
                    int mode, int intercept, double alpha, double reg, int reg_mode, int nonneg,
                    int max_rounds, int n_new, const long long* off, const int* idx,
                    const double* r, double* x_out, int* status, int* rounds) {
-  MR_CHECK(k >= 1 && k <= kMaxK, "fold-in: k must be in 1..128");
-  MR_CHECK(mode == MR_FOLD_EXPLICIT || mode == MR_FOLD_IMPLICIT, "fold-in: unknown mode");
-  MR_CHECK(intercept == 0 || intercept == 1, "fold-in: intercept must be 0 or 1");
   MR_CHECK(nonneg == 0 || nonneg == 1, "fold-in: nonneg must be 0 or 1");
-  const bool implicit = mode == MR_FOLD_IMPLICIT;
-  MR_CHECK(!implicit || (!intercept && !row_offset),
-           "fold-in: the implicit mode takes no intercept and no row_offset");
-  MR_CHECK(reg_mode == MR_REG_CONSTANT || reg_mode == MR_REG_WEIGHTED,
-           "fold-in: unknown regularization mode");
-  MR_CHECK(std::isfinite(alpha) && alpha >= 0.0, "fold-in: alpha must be finite and >= 0");
-  MR_CHECK(std::isfinite(reg) && reg >= 0.0, "fold-in: reg must be finite and >= 0");
   MR_CHECK(max_rounds >= 0, "fold-in: max_rounds must be >= 0");
-  MR_CHECK(n_new >= 0 && n_rows >= 0, "fold-in: negative sizes");
+  if (fi_validate("fold-in", k, n_rows, T, row_offset, mode, intercept, alpha, reg, reg_mode,
+                  n_new, off, idx, r))
+    return -1;
   if (n_new == 0) return 0;
-  MR_CHECK(off && x_out, "fold-in: off and x_out are required");
-  MR_CHECK(rk_offsets_ok(off, n_new), "fold-in: offsets must start at 0 and not decrease");
+  MR_CHECK(x_out, "fold-in: x_out is required");
+  const bool implicit = mode == MR_FOLD_IMPLICIT;
   const int64_t nnz = off[n_new];
-  MR_CHECK(nnz == 0 || (idx && r), "fold-in: idx and r are required");
-  MR_CHECK(n_rows == 0 || T, "fold-in: T is required");
-  for (int e = 0; e < n_new; ++e)
-    MR_CHECK(off[e + 1] - off[e] < 0x7fffffff, "fold-in: list too long");
-  for (int64_t i = 0; i < nnz; ++i) {
-    MR_CHECK(idx[i] >= 0 && idx[i] < n_rows, "fold-in: id out of range");
-    MR_CHECK(std::isfinite(r[i]), "fold-in: r must be finite");
-    MR_CHECK(!implicit || r[i] >= 0.0, "fold-in: r must be >= 0 in the implicit mode");
-  }
-  MR_CHECK(all_finite(T, (int64_t)n_rows * k), "fold-in: T must be finite");
-  MR_CHECK(!row_offset || all_finite(row_offset, n_rows), "fold-in: row_offset must be finite");
 
   const int K = k + intercept;
   const int cap = max_rounds > 0 ? max_rounds : 4 * (k + 1);
@@ -408,11 +272,11 @@ static int fold_in(int device, int k, int n_rows, const double* T, const double*
   const int weighted = reg_mode == MR_REG_WEIGHTED ? 1 : 0;
   const size_t W = (size_t)K + 1, WS = (size_t)K + 2, gbytes = (size_t)K * W * sizeof(double);
   if (!nonneg) {
-    // LDS: G [K][K+1] plus a row stage of up to 32 rows (fewer at K >= 128)
-    const size_t budget = 150 * 1024;
-    MR_CHECK(gbytes + 8 * WS * sizeof(double) <= budget, "fold-in: k too large");
-    const int rows = (int)std::min<size_t>(32, (budget - gbytes) / (WS * sizeof(double)));
-    const size_t lds = gbytes + (size_t)rows * WS * sizeof(double);
+    int rows;
+    size_t gb, stage;
+    fi_solve_lds(K, &rows, &gb, &stage);
+    MR_CHECK(rows > 0, "fold-in: k too large");
+    const size_t lds = gb + stage;
     if (lds > 64 * 1024)
       MR_HIP(hipFuncSetAttribute((const void*)fold_build_kernel<true>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -167,6 +167,28 @@ class ImplicitModel:
         return general(self.X, lists, "implicit", alpha=self.alpha, reg=self.reg,
                        reg_mode=self.reg_mode, nonneg=self.nonneg, device=self.device)[:2]
 
+    def _explain(self, table, lists, targets, top, full):
+        if self.nonneg:
+            raise ValueError("explanations cover the unconstrained solve only: a model with "
+                             "nonneg=True is not supported")
+        from .foldin import explain
+        return explain(table, lists, targets, "implicit", alpha=self.alpha, reg=self.reg,
+                       reg_mode=self.reg_mode, top=top, full=full, device=self.device)
+
+    def explain(self, lists, targets, top=10, full=False):
+        """Why items score what they score for folded-in users: per user of
+        ``lists`` (as ``fold_in`` takes them) and per item of ``targets[u]``
+        the ``top`` entries of the user's own list by their contribution to
+        ``x_u . Y[t]`` (``foldin.explain``; the contributions of a target sum
+        to its score).  Returns a ``foldin.Explanation``.  A model with
+        ``nonneg=True`` raises ``ValueError``."""
+        return self._explain(self.Y, lists, targets, top, full)
+
+    def explain_items(self, lists, targets, top=10, full=False):
+        """``explain`` for folded-in items: ``lists`` hold ``(user, r)``,
+        ``targets`` users of X."""
+        return self._explain(self.X, lists, targets, top, full)
+
     def rank_eval(self, test, exclude=None, n=10, weights=None):
         """``ranking.rank_eval`` of the model's own users on held-out pairs."""
         from .ranking import rank_eval

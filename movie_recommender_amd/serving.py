@@ -167,6 +167,53 @@ class MovieTable:
         valid = np.array([len(l) > 0 for l in lists], bool)
         return valid, X, status
 
+    def explain_ridge(self, rating_lists, movie_ids_per_user, reg, reg_mode="weighted",
+                      subtract_median=True, top=10):
+        """"Because you rated ...": per user of ``rating_lists`` (as
+        ``fold_in_ridge`` takes and maps them) and per movie id of
+        ``movie_ids_per_user[u]``, the ``top`` rated movies by their
+        contribution to the movie's score (``foldin.explain`` on the system of
+        ``fold_in_ridge``).  Target ids that are not ALS movies are dropped
+        and reported.  The score is ``V[t] . x[:k] + x[k]``: what ``scores``
+        gives before it adds the movie's median, and what the contributions of
+        a target sum to.  Returns ``(valid bool[B], explanations, dropped)``:
+        ``explanations[u]`` maps a kept target movie id to ``(score, [(rated
+        movie id, contribution)])``, largest contribution first;
+        ``dropped[u]`` lists the target ids that were dropped."""
+        from .foldin import explain
+        reg = float(reg)
+        if not reg > 0.0:
+            raise ValueError("explain_ridge needs reg > 0")
+        rating_lists = [list(l) for l in rating_lists]
+        movie_ids_per_user = [list(t) for t in movie_ids_per_user]
+        if len(movie_ids_per_user) != len(rating_lists):
+            raise ValueError("movie_ids_per_user must hold one list of movie ids per user")
+        med = np.zeros(self.n_als)
+        if subtract_median:
+            med[self.cand_als] = self.cand_med
+        lists, kept_mids, targets, kept_t, dropped = [], [], [], [], []
+        for lst, tg in zip(rating_lists, movie_ids_per_user):
+            kept = [(mid, float(r)) for mid, r in lst
+                    if mid in self.als_movie_ids
+                    and (not subtract_median or mid in self.movie_medians)]
+            lists.append([(self.als_movie_ids[mid], r) for mid, r in kept])
+            kept_mids.append([mid for mid, _ in kept])
+            kept_t.append([mid for mid in tg if mid in self.als_movie_ids])
+            dropped.append([mid for mid in tg if mid not in self.als_movie_ids])
+            targets.append([self.als_movie_ids[mid] for mid in kept_t[-1]])
+        ex = explain(self._V.reshape(self.n_als, self.k), lists, targets, "explicit", True,
+                     med if subtract_median else None, 0.0, reg, reg_mode, top,
+                     device=self.device)
+        out = []
+        for u in range(len(lists)):
+            per = {}
+            for q, mid in enumerate(kept_t[u]):
+                per[mid] = (float(ex.score[u][q]),
+                            [(kept_mids[u][pos], val) for _, pos, val in ex.top[u][q]])
+            out.append(per)
+        valid = np.array([len(l) > 0 for l in lists], bool)
+        return valid, out, dropped
+
     # -- scoring ------------------------------------------------------------
     def scores(self, X):
         """``predict`` of every candidate movie for each user row of ``X``
