@@ -1352,23 +1352,46 @@ __device__ __forceinline__ void gram_wave(
   // register copy there ever waits on a load in flight.
   const int64_t safe = wlen > 0 ? wbeg : 0;    // an address every wave may read
   const int slot = half_slot(lane);
+  // NB <= 4: positions relative to the work item, in 32 bits.  Whether rating
+  // 32 c + slot exists is one compare of the lane's slot against a scalar,
+  // and the half's base address is scalar arithmetic, clamped into the work
+  // item so that a masked lane (offset 0) still reads one of its entries.
+  // That leaves the vector ALU a compare and a select per load instead of
+  // 64-bit adds, compares and shifts every half (the loop is bound by vector
+  // issue).  A masked lane loads another in-range entry than the 64-bit form
+  // does; fin32 / bias32 discard it either way.
+  const int32_t* __restrict__ idxw = idx + safe;
+  const float* __restrict__ valw = val + safe;
+  auto ok32 = [&](int c) {
+    if constexpr (NB <= 4) return slot < wlen - 32 * c;
+    else return wbeg + 32 * (int64_t)c + slot < end;
+  };
   auto ld32 = [&](int c) {
-    const int64_t jj = wbeg + 32 * (int64_t)c + slot;
     ChunkRaw r;
-    const int64_t js = jj < end ? jj : safe;
-    r.idx = idx[js];
-    r.r = val[js];
+    if constexpr (NB <= 4) {
+      const int last = wlen > 0 ? wlen - 1 : 0;
+      const int cs = 32 * c < last ? 32 * c : last;
+      const uint32_t o = ok32(c) ? (uint32_t)slot : 0u;
+      r.idx = (idxw + cs)[o];
+      r.r = (valw + cs)[o];
+    } else {
+      const int64_t jj = wbeg + 32 * (int64_t)c + slot;
+      const int64_t js = jj < end ? jj : safe;
+      r.idx = idx[js];
+      r.r = val[js];
+    }
     r.b = 0.f;
     return r;
   };
   auto bias32 = [&](ChunkRaw& cr, int c) {
     if (!USER) {
-      const bool ok = wbeg + 32 * (int64_t)c + slot < end;
-      cr.b = bias[ok ? cr.idx : zrow];
+      const bool ok = ok32(c);
+      if constexpr (NB <= 4) cr.b = bias[(uint32_t)(ok ? cr.idx : zrow)];   // ids are >= 0
+      else cr.b = bias[ok ? cr.idx : zrow];
     }
   };
   auto fin32 = [&](const ChunkRaw& cr, int c) {
-    const bool ok = wbeg + 32 * (int64_t)c + slot < end;
+    const bool ok = ok32(c);
     ChunkRegs r;
     r.idx = ok ? cr.idx : zrow;
     r.w = ok ? cr.r - cr.b : 0.f;
@@ -1390,6 +1413,11 @@ __device__ __forceinline__ void gram_wave(
     const ChunkRaw h3 = ld32(h + 3);
     bias32(h2, h + 2);
     gather_half<NB, BUF>(Fr, w, fin32(h1, h + 1), src, row_bytes);
+    // NB <= 4: every row fetch of half h+1 is issued before the first MFMA of
+    // half h, so the whole phase lies between issue and first use.  Without
+    // this barrier the machine scheduler sank the eight gathers behind three
+    // quarters of the phase's MFMAs (DESIGN.md "What bounds the Gram").
+    if constexpr (NB <= 4) __builtin_amdgcn_sched_barrier(0);
     bf3_mfma<NB, USER>(acc, accw, P, W, rhs_mfma);
     __builtin_amdgcn_sched_barrier(0);
     bf3_split<NB, USER>(P, W, cacc, sacc, wsum, Fr, w, rhs_mfma);
