@@ -9,6 +9,7 @@ Modules
   engine      device-resident ALS context (``include/mr_als.h``)
   implicit    implicit-feedback (confidence-weighted) ALS on the same context
   foldin      new users / items for every model kind (``include/mr_foldin.h``)
+  content     tag least-squares content model (``include/mr_content.h``)
   distributed one process per GPU, users/items sharded, factor all-gather
   synth       seeded MovieLens-shaped ratings (benchmarks, statistical tests)
   build       compiles ``lib/cpp_ls_lib.so`` with hipcc for gfx950

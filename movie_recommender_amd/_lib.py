@@ -7,8 +7,9 @@ device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_prep.h``), the similar-movies database
 (``include/mr_similar.h``), the ranking evaluation / implicit fold-in
 (``include/mr_ranking.h``), the general fold-in
-(``include/mr_foldin.h``) and the explanations
-(``include/mr_explain.h``).  There is no CPU
+(``include/mr_foldin.h``), the explanations
+(``include/mr_explain.h``) and the content model
+(``include/mr_content.h``).  There is no CPU
 fallback: if the library is missing or cannot load, every entry point raises.
 """
 import ctypes
@@ -229,6 +230,19 @@ SIGNATURES = {
                                   ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                   ctypes.c_int, LLP, IP, DP, LLP, IP, ctypes.c_int, DP, IP, DP,
                                   LLP, DP, IP, DP, IP]),
+    # content model (include/mr_content.h)
+    "mr_content_create": (VP, [ctypes.c_int, ctypes.c_int, IP, DP, LLP, IP, DP]),
+    "mr_content_destroy": (None, [VP]),
+    "mr_content_num_candidates": (ctypes.c_int, [VP]),
+    "mr_content_fit": (ctypes.c_int, [VP, ctypes.c_int, LLP, IP, DP, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_int, IP, IP, IP,
+                                      DP, IP, IP]),
+    "mr_content_scores": (ctypes.c_int, [VP, ctypes.c_int, IP, IP, DP, DP]),
+    "mr_content_top_n": (ctypes.c_int, [VP, ctypes.c_int, IP, IP, DP, LLP, IP, ctypes.c_int, IP,
+                                        DP, IP]),
+    "mr_content_evaluate": (ctypes.c_int, [VP, ctypes.c_int, IP, IP, DP, LLP, IP, DP, DP, LLP,
+                                           LLP, DP, DP, LLP]),
+    "mr_content_last_kernel_ms": (ctypes.c_int, [VP, DP]),
     "mr_last_error": (ctypes.c_char_p, []),
     "mr_device_count": (ctypes.c_int, []),
     "mr_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),

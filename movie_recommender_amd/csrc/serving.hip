@@ -19,36 +19,11 @@
 #include "../../include/mr_als.h"
 #include "../../include/mr_serving.h"
 #include "mr_internal.h"
+#include "serving_device.h"
 
 namespace mr {
 
-// ---------------------------------------------------------------------------
-// fp64 helpers
-// ---------------------------------------------------------------------------
-// The reference's Python evaluates u*v and s + (u*v) as two correctly rounded
-// operations.  hipcc contracts a*b + c into v_fmac_f64 by default, which
-// changes the last bit, so contraction is switched off for these two.
-__device__ __forceinline__ double mul_rn(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ double add_rn(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// Order-preserving 64-bit key of a score (larger score -> larger key); -0.0
-// and +0.0 map to the same key as they compare equal in Python's sort.  Key 0
-// is reserved for "excluded" (it would be a negative NaN with every bit set).
-__device__ __forceinline__ uint64_t score_key(double s) {
-  if (s == 0.0) s = 0.0;
-  const uint64_t b = (uint64_t)__double_as_longlong(s);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_score(uint64_t key) {
-  const uint64_t b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-  return __longlong_as_double((long long)b);
-}
+// fp64 helpers (mul_rn, add_rn, score_key, key_score): serving_device.h
 
 template <typename T>
 __device__ __forceinline__ T wave_sum_t(T v) {
@@ -900,66 +875,30 @@ static int rec_top_n(Rec* r, int n_users, const double* Xh, const long long* exc
     return 0;
   }
   const int K = r->k + 1;
-  const int64_t B = std::min<int64_t>(user_chunk(r), n_users);
-  DBuf<double> X, osc;
-  DBuf<uint64_t> S;
-  DBuf<unsigned long long> kmin, kmax;
-  DBuf<int> omid, ocnt, ecand;
-  DBuf<int64_t> eoff;
-  if (X.alloc(B * K) || S.alloc(B * r->n_cand) || osc.alloc(B * N) || omid.alloc(B * N) ||
-      ocnt.alloc(B) || eoff.alloc(B + 1) || kmin.alloc(B) || kmax.alloc(B))
-    return -1;
-  int64_t max_ex = 0;
-  if (excl_off) {
-    for (int64_t u0 = 0; u0 < n_users; u0 += B) {
-      const int64_t nb = std::min<int64_t>(B, n_users - u0);
-      max_ex = std::max<int64_t>(max_ex, excl_off[u0 + nb] - excl_off[u0]);
-    }
-    for (int64_t i = 0; i < excl_off[n_users]; ++i)
-      MR_CHECK(excl_cand[i] >= 0 && excl_cand[i] < r->n_cand, "rec: excluded candidate out of range");
-    if (ecand.alloc(max_ex)) return -1;
-  }
-  std::vector<int64_t> loc;
-  for (int64_t u0 = 0; u0 < n_users; u0 += B) {
-    const int nb = (int)std::min<int64_t>(B, n_users - u0);
-    MR_H2D(X.p, Xh + u0 * K, (size_t)nb * K * 8, r->stream);
-    const dim3 grid((nb + SC_U - 1) / SC_U, (r->n_cand + SC_C - 1) / SC_C);
-    MR_CHECK(grid.y <= 65535, "rec: more than 65535 * 256 candidates");
-    if (timed(r, RT_SCORE, [&]() {
-          rec_range_init_kernel<<<(nb + 255) / 256, 256, 0, r->stream>>>(nb, kmin.p, kmax.p);
+  DBuf<double> X;
+  if (X.alloc(std::min<int64_t>(user_chunk(r), n_users) * K)) return -1;
+  const dim3 cgrid(1, (r->n_cand + SC_C - 1) / SC_C);
+  MR_CHECK(cgrid.y <= 65535, "rec: more than 65535 * 256 candidates");
+  return top_n_chunked(
+      "rec", r->stream, r->n_cand, r->mid, n_users, user_chunk(r), excl_off, excl_cand, N, out_mid,
+      out_score, out_count,
+      [&](int64_t u0, int nb, uint64_t* keys, unsigned long long* kmin,
+          unsigned long long* kmax) -> int {
+        MR_H2D(X.p, Xh + u0 * K, (size_t)nb * K * 8, r->stream);
+        const dim3 grid((nb + SC_U - 1) / SC_U, cgrid.y);
+        return timed(r, RT_SCORE, [&]() {
+          rec_range_init_kernel<<<(nb + 255) / 256, 256, 0, r->stream>>>(nb, kmin, kmax);
           rec_score_kernel<true><<<grid, 256, 0, r->stream>>>(nb, r->n_cand, r->k, X.p, r->Vc,
-                                                              r->med, S.p, r->n_cand, kmin.p,
-                                                              kmax.p);
+                                                              r->med, keys, r->n_cand, kmin, kmax);
           return 0;
-        }))
-      return -1;
-    if (excl_off) {
-      loc.assign(nb + 1, 0);
-      for (int i = 0; i <= nb; ++i) loc[i] = excl_off[u0 + i] - excl_off[u0];
-      MR_H2D(eoff.p, loc.data(), (nb + 1) * 8, r->stream);
-      if (loc[nb] > 0)
-        MR_H2D(ecand.p, excl_cand + excl_off[u0], loc[nb] * 4, r->stream);
-      if (timed(r, RT_EXCL, [&]() {
-            rec_exclude_kernel<<<nb, 256, 0, r->stream>>>(S.p, r->n_cand, eoff.p, ecand.p);
-            return 0;
-          }))
-        return -1;
-    }
-    if (timed(r, RT_SELECT, [&]() {
-          rec_select_kernel<<<nb, SEL_NT, 0, r->stream>>>(S.p, r->n_cand, r->n_cand, r->mid,
-                                                          kmin.p, kmax.p, N, omid.p, osc.p,
-                                                          ocnt.p);
+        });
+      },
+      [&](int stage, auto&& launch) {
+        return timed(r, stage == TOPN_EXCL ? RT_EXCL : RT_SELECT, [&]() {
+          launch();
           return 0;
-        }))
-      return -1;
-    MR_D2H(out_mid + u0 * N, omid.p, (size_t)nb * N * 4, r->stream);
-    MR_D2H(out_score + u0 * N, osc.p, (size_t)nb * N * 8, r->stream);
-    MR_D2H(out_count + u0, ocnt.p, (size_t)nb * 4, r->stream);
-  }
-  MR_HIP(hipStreamSynchronize(r->stream));
-  for (int u = 0; u < n_users; ++u)
-    MR_CHECK(out_count[u] >= 0, "rec: top-N candidate buffer overflow (internal)");
-  return 0;
+        });
+      });
 }
 
 static int rec_fold_in(Rec* r, int n_users, const long long* off, const int* als_idx,
@@ -1099,6 +1038,35 @@ static int rank_agreement(int device, int n_users, const long long* off, const d
   if (n_dis) MR_D2H(n_dis, ddis.p, n_users * 8, s);
   MR_HIP(hipStreamSynchronize(s));
   return 0;
+}
+
+// Launchers for content.hip (serving_device.h) ---------------------------------
+static_assert(kRecMaxResults == SEL_CAP / 2, "select keeps at most half its buffer");
+
+void launch_rec_range_init(hipStream_t s, int n, unsigned long long* kmin,
+                           unsigned long long* kmax) {
+  rec_range_init_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, kmin, kmax);
+}
+
+void launch_rec_exclude(hipStream_t s, int n_users, uint64_t* keys, int64_t ld,
+                        const int64_t* off, const int* cand) {
+  rec_exclude_kernel<<<n_users, 256, 0, s>>>(keys, ld, off, cand);
+}
+
+void launch_rec_select(hipStream_t s, int n_users, const uint64_t* keys, int64_t ld, int n_cand,
+                       const int* mid, const unsigned long long* kmin,
+                       const unsigned long long* kmax, int N, int* out_mid, double* out_score,
+                       int* out_count) {
+  rec_select_kernel<<<n_users, SEL_NT, 0, s>>>(keys, ld, n_cand, mid, kmin, kmax, N, out_mid,
+                                               out_score, out_count);
+}
+
+void launch_rank_agreement(hipStream_t s, int n_users, const int64_t* off, const double* actual,
+                           double* pred, double* agreement, long long* n_agree,
+                           long long* n_dis, double* sse, long long* n_pred) {
+  rec_eval_kernel<false><<<n_users, 256, 0, s>>>(0, nullptr, nullptr, off, nullptr, actual,
+                                                 nullptr, nullptr, pred, agreement, n_agree, n_dis,
+                                                 sse, n_pred);
 }
 
 }  // namespace mr

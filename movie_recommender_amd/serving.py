@@ -371,12 +371,17 @@ class ALS_Model:
 
 def get_recommendations(model, user_ratings_dict, num_results=ROTATION_SIZE * 100,
                         rotation=0):
-    """``recommend.py:86-115`` for a model built by ``ALS_Model``: the first
-    ``num_results`` unrated movies by (score, movie id) descending, and the
-    ``rotation``-th slice ``[rotation::4]`` the app returns.  Returns
-    ``(rotation_slice, full_list)`` of movie ids."""
+    """``recommend.py:86-115`` for a model built by ``ALS_Model`` or by
+    ``content.TagLS_UserProfile``: the first ``num_results`` unrated movies by
+    (score, movie id) descending, and the ``rotation``-th slice
+    ``[rotation::4]`` the app returns.  Returns ``(rotation_slice,
+    full_list)`` of movie ids."""
+    from .content import TagLS_UserProfile
     if not model.is_valid():
         raise ValueError("Unable to create model for this algorithm.")
-    top = model._table.top_n(model.user_factors, [user_ratings_dict], num_results)[0]
+    if isinstance(model, TagLS_UserProfile):
+        top = model._table.top_n(model._fit, [user_ratings_dict], num_results)[0]
+    else:
+        top = model._table.top_n(model.user_factors, [user_ratings_dict], num_results)[0]
     movie_ids = [m for _, m in top]
     return movie_ids[rotation::ROTATION_SIZE], movie_ids
