@@ -8,8 +8,8 @@ device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_similar.h``), the ranking evaluation / implicit fold-in
 (``include/mr_ranking.h``), the general fold-in
 (``include/mr_foldin.h``), the explanations
-(``include/mr_explain.h``) and the content model
-(``include/mr_content.h``).  There is no CPU
+(``include/mr_explain.h``) and the content models
+(``include/mr_content.h``, ``include/mr_tagcount.h``).  There is no CPU
 fallback: if the library is missing or cannot load, every entry point raises.
 """
 import ctypes
@@ -105,6 +105,8 @@ DP = ctypes.POINTER(ctypes.c_double)
 FP = ctypes.POINTER(ctypes.c_float)
 LLP = ctypes.POINTER(ctypes.c_longlong)
 VP = ctypes.c_void_p
+
+_TC_MODEL = [DP, LLP, IP, DP, DP, DP, IP, IP]   # a tag-count model's eight arrays
 
 # name -> (restype, argtypes); every symbol of include/*.h
 SIGNATURES = {
@@ -243,6 +245,20 @@ SIGNATURES = {
     "mr_content_evaluate": (ctypes.c_int, [VP, ctypes.c_int, IP, IP, DP, LLP, IP, DP, DP, LLP,
                                            LLP, DP, DP, LLP]),
     "mr_content_last_kernel_ms": (ctypes.c_int, [VP, DP]),
+    # content model: tag counting (include/mr_tagcount.h); a model is
+    # (genre_profile, tp_off, tp_idx, tp_val, x0, x1, has0, has1)
+    "mr_tagcount_create": (VP, [ctypes.c_int, ctypes.c_int, IP, DP, LLP, IP, LLP, IP, DP,
+                                ctypes.c_int, DP, ctypes.c_int, DP]),
+    "mr_tagcount_destroy": (None, [VP]),
+    "mr_tagcount_num_candidates": (ctypes.c_int, [VP]),
+    "mr_tagcount_fit": (ctypes.c_int, [VP, ctypes.c_int, LLP, IP, DP, DP, LLP, IP, DP,
+                                       ctypes.c_longlong, DP, DP, IP, IP, IP, IP, IP]),
+    "mr_tagcount_scores": (ctypes.c_int, [VP, ctypes.c_int] + _TC_MODEL + [DP]),
+    "mr_tagcount_top_n": (ctypes.c_int, [VP, ctypes.c_int] + _TC_MODEL
+                          + [LLP, IP, ctypes.c_int, IP, DP, IP]),
+    "mr_tagcount_evaluate": (ctypes.c_int, [VP, ctypes.c_int] + _TC_MODEL
+                             + [LLP, IP, DP, DP, LLP, LLP, DP, DP, LLP]),
+    "mr_tagcount_last_kernel_ms": (ctypes.c_int, [VP, DP]),
     "mr_last_error": (ctypes.c_char_p, []),
     "mr_device_count": (ctypes.c_int, []),
     "mr_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),

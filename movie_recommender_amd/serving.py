@@ -371,15 +371,16 @@ class ALS_Model:
 
 def get_recommendations(model, user_ratings_dict, num_results=ROTATION_SIZE * 100,
                         rotation=0):
-    """``recommend.py:86-115`` for a model built by ``ALS_Model`` or by
-    ``content.TagLS_UserProfile``: the first ``num_results`` unrated movies by
-    (score, movie id) descending, and the ``rotation``-th slice
-    ``[rotation::4]`` the app returns.  Returns ``(rotation_slice,
-    full_list)`` of movie ids."""
+    """``recommend.py:86-115`` for a model built by ``ALS_Model``, by
+    ``content.TagLS_UserProfile`` or by ``tagcount.TagCount_UserProfile``: the
+    first ``num_results`` unrated movies by (score, movie id) descending, and
+    the ``rotation``-th slice ``[rotation::4]`` the app returns.  Returns
+    ``(rotation_slice, full_list)`` of movie ids."""
     from .content import TagLS_UserProfile
+    from .tagcount import TagCount_UserProfile
     if not model.is_valid():
         raise ValueError("Unable to create model for this algorithm.")
-    if isinstance(model, TagLS_UserProfile):
+    if isinstance(model, (TagLS_UserProfile, TagCount_UserProfile)):
         top = model._table.top_n(model._fit, [user_ratings_dict], num_results)[0]
     else:
         top = model._table.top_n(model.user_factors, [user_ratings_dict], num_results)[0]
