@@ -410,8 +410,22 @@ __global__ __launch_bounds__(SEL_NT) void rec_select_kernel(
 // Rows [V_m, 1 | r] are staged FI_R at a time; each thread owns NE entries of
 // the upper triangle of [G | c] (K = k+1 columns + rhs) and accumulates them
 // in registers in row order; then G is formed in LDS and factored.
-// Pivot ratio below `cond_limit` (or a non-positive pivot) flags the user for
-// the SVD path (method 2).
+// Pivot ratio (min / max Cholesky pivot) below `cond_limit`, or a non-positive
+// pivot, flags the user for the SVD path (method 2).
+//
+// cond_limit = 1e-6 (rec_fold_in).  Normal equations err by about eps / ratio
+// against the exact least-squares answer, Jacobi by about eps * cond.  Measured
+// on an MI355X against 60-digit answers (880 random lists, k = 3 and 11,
+// M = 40, column 1 approaching column 0, half-star ratings), worst error of a
+// list that took Cholesky:
+//   limit 1e-8 (before): 1.0e-7 at ratio 1.2e-8; above the promised 1e-8 on
+//     75 of the 240 lists with ratios 1.2e-8 .. 5e-8;
+//   limit 1e-6 (now):    7.6e-10 at ratio 1e-6 (2.0e-10 at 4e-6); the same
+//     lists through Jacobi: 7.7e-12 at worst.
+// Ordinary lists are nowhere near either limit: of the golden fixtures' 41
+// valid lists 3 go to Jacobi (the rank-deficient ones) and of
+// test_fold_in_sizes' 21 none, before and after; the smallest ratio among the
+// rest is 2.8e-4.
 // ---------------------------------------------------------------------------
 constexpr int FI_NE = 9;   // entries per thread per pass (no spills at 256 threads)
 
@@ -575,6 +589,26 @@ __global__ __launch_bounds__(256) void fold_in_svd_kernel(
     z = (sh[2][0] + sh[2][1]) + (sh[2][2] + sh[2][3]);
     __syncthreads();
   };
+  // Rotation floor.  A column that is null up to rounding never meets the
+  // relative test below (noise is not orthogonal to anything), so a list with
+  // fewer distinct rows than K ran all 60 sweeps: 449 ms against 113 ms for a
+  // constant-column list at k = 128, M = 301.  Pairs with a column at or below
+  // eps * K * (the largest column norm before the first sweep, a lower bound
+  // of s_max) are skipped.  Such a column is under the cut-off at the end
+  // (K <= max(M, K)), and leaving it unrotated turns a kept column p by at
+  // most floor / |a_p|, i.e. K eps cond in x.  The cut-off's own scale,
+  // eps * max(M, K), is too coarse when M >> K: 4.1e-14 against lstsq's
+  // 2.1e-15 at k = 3, M = 301.
+  double n0 = 0.0;
+  for (int i = 0; i < K; ++i) {
+    double nn = 0.0, y = 0.0, z = 0.0;
+    const double* ai = A + (int64_t)i * M;
+    for (int r = tid; r < M; r += 256) nn = fma(ai[r], ai[r], nn);
+    sum3(nn, y, z);
+    n0 = fmax(n0, nn);
+  }
+  const double epsn = 2.220446049250313e-16 * (double)K;
+  const double floor2 = epsn * epsn * n0;
   for (int sweep = 0; sweep < 60; ++sweep) {
     if (tid == 0) s_rot = 0;
     __syncthreads();
@@ -590,7 +624,8 @@ __global__ __launch_bounds__(256) void fold_in_svd_kernel(
           ga = fma(x, y, ga);
         }
         sum3(al, be, ga);
-        if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
+        if (ga == 0.0 || al <= floor2 || be <= floor2 || fabs(ga) <= 1e-15 * sqrt(al * be))
+          continue;
         const double zeta = (be - al) / (2.0 * ga);
         const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
         const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
@@ -925,7 +960,7 @@ static int rec_fold_in(Rec* r, int n_users, const long long* off, const int* als
   MR_CHECK(gbytes + 8 * (K + 1) * sizeof(double) <= budget, "rec: fold-in k too large");
   const int rows = (int)std::min<size_t>(32, (budget - gbytes) / ((K + 1) * sizeof(double)));
   const size_t lds = gbytes + (size_t)rows * (K + 1) * sizeof(double);
-  const double cond_limit = 1e-8;
+  const double cond_limit = 1e-6;
   if (lds > 64 * 1024)
     MR_HIP(hipFuncSetAttribute((const void*)fold_in_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
