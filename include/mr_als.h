@@ -107,7 +107,8 @@ typedef struct mr_comm {
 
 /* Context from host COO ratings (zero-based ids).  Builds the by-user and
  * by-item CSR on the device.  k <= 512 (k > 128 runs the streamed large-k
- * kernels; the exact solver needs k <= 128).  NULL on error (mr_last_error). */
+ * kernels; the exact solvers need k <= 128, the Cholesky solver only while
+ * MR_OPT_SOLVE_BLOCKED is 0).  NULL on error (mr_last_error). */
 mr_als* mr_als_create(int device, int k, int num_users, int num_items,
                       long long n_ratings, const int* user_ids,
                       const int* item_ids, const double* ratings);
@@ -176,9 +177,18 @@ int mr_als_get_factors(mr_als* ctx, double* U, double* V);
  * stream).  For workloads whose host tables would be multi-GB (C5). */
 int mr_als_init_factors(mr_als* ctx, unsigned long long seed);
 
-/* MR_SOLVER_NNLS is refused (-1, context unchanged) on a sharded context; like
- * the Cholesky solver it needs k <= 128 (a half-step with a larger k fails). */
+/* MR_SOLVER_NNLS is refused (-1, context unchanged) on a sharded context and
+ * needs k <= 128 (a half-step with a larger k fails).  MR_SOLVER_CHOLESKY needs
+ * k <= 128 while MR_OPT_SOLVE_BLOCKED is 0 (the default: K x K fp64 in LDS);
+ * with MR_OPT_SOLVE_BLOCKED = 1 it runs for every 1 <= k <= 512. */
 int mr_als_set_solver(mr_als* ctx, int solver, double ridge);
+/* Scratch of the blocked exact solve (MR_OPT_SOLVE_BLOCKED) for one side: out =
+ * {K, tiles, bytes_per_slot} with K = k + 1 on the user side (user_side != 0),
+ * k on the item side, T = ceil(K / 16), tiles = T (T + 1) / 2 fp64 tiles of
+ * 16 x 16 and bytes_per_slot = 2048 tiles (the rhs and the pivots stay on the
+ * chip).  A pure host function; the engine sizes its scratch from it.  -1 for
+ * k outside 1 ... 512 or a NULL out. */
+int mr_solve_plan(int k, int user_side, long long out[3]);
 /* The non-negative solver (MR_SOLVER_NNLS): per local entity, Kim and Park's
  * block principal pivoting with their backup rule on the side's normal
  * equations as last built (Gram, + S in implicit mode, + lambda ridge, + the
@@ -300,10 +310,25 @@ int mr_als_set_timing(mr_als* ctx, int enable);
  *                         waits once per solve); 0: one launch per
  *                         iteration.  Results are identical.  Ranks that
  *                         share one GPU must set 0 (their resident grids
- *                         would wait on each other): distributed.py does */
+ *                         would wait on each other): distributed.py does
+ *   MR_OPT_SOLVE_BLOCKED  0 (default): MR_SOLVER_CHOLESKY half-steps hold
+ *                         K x K fp64 in LDS and need k <= 128; 1: they run
+ *                         the blocked kernel (a tiled factorisation on the
+ *                         fp64 matrix instruction, the factor in a global
+ *                         scratch allocated at the first such solve) for
+ *                         every 1 <= k <= 512, on both sides, sharded or not.
+ *                         Other values are rejected.  MR_SOLVER_CG and
+ *                         MR_SOLVER_NNLS are not affected
+ *   MR_OPT_SOLVE_SLOTS    scratch slots of the blocked kernel = entities in
+ *                         flight: 0 (default) automatic, min(entities,
+ *                         2 x CUs, 256 MiB / slot); 1 ... 4096 forced.  Results
+ *                         do not depend on it.  It exists so that a test can
+ *                         make a few entities wrap around the slots; it is
+ *                         not a tuning knob */
 enum { MR_OPT_FUSE_START = 0, MR_OPT_CG_SPECULATE = 1, MR_OPT_WAIT_TIMEOUT_S = 2,
        MR_OPT_CG_ONEPASS = 3, MR_OPT_GRAM_RHS_MFMA = 4, MR_OPT_CG_SWEEP = 5,
-       MR_OPT_PEER_TIMEOUT_S = 6, MR_OPT_CG_TILE_NT = 7, MR_OPT_CG_RESIDENT = 8 };
+       MR_OPT_PEER_TIMEOUT_S = 6, MR_OPT_CG_TILE_NT = 7, MR_OPT_CG_RESIDENT = 8,
+       MR_OPT_SOLVE_BLOCKED = 9, MR_OPT_SOLVE_SLOTS = 10 };
 int mr_als_set_option(mr_als* ctx, int option, double value);
 /* Ratings per Gram work item: heavier entities are split across waves and
  * their partial normal equations combined in order.  Applies to contexts

@@ -142,6 +142,7 @@ SIGNATURES = {
     "mr_als_set_factors": (ctypes.c_int, [VP, DP, DP]),
     "mr_als_get_factors": (ctypes.c_int, [VP, DP, DP]),
     "mr_als_set_solver": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_double]),
+    "mr_solve_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, LLP]),
     "mr_als_set_nnls": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_int]),
     "mr_als_nnls_stats": (ctypes.c_int, [VP, ctypes.c_int, LLP]),
     "mr_als_nnls_rounds": (ctypes.c_int, [VP, ctypes.c_int, IP]),

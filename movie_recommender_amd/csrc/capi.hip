@@ -291,6 +291,17 @@ int mr_als_set_solver(mr_als* ctx, int solver, double ridge) {
   return 0;
 }
 
+int mr_solve_plan(int k, int user_side, long long out[3]) {
+  MR_CHECK(out, "mr_solve_plan: null argument");
+  MR_CHECK(k >= 1 && k <= mr::kMaxKLarge, "mr_solve_plan: k must be in [1, 512]");
+  const int K = k + (user_side ? 1 : 0);
+  const long long T = (K + 15) / 16;
+  out[0] = K;
+  out[1] = T * (T + 1) / 2;
+  out[2] = mr::solve_slot_bytes(K);
+  return 0;
+}
+
 int mr_als_set_nnls(mr_als* ctx, int max_rounds, int warm_start) {
   MR_CHECK(ctx, "mr_als_set_nnls: null context");
   MR_CHECK(max_rounds >= 0, "mr_als_set_nnls: max_rounds must be >= 0 (0: the default)");
@@ -373,6 +384,15 @@ int mr_als_set_option(mr_als* ctx, int option, double value) {
       return 0;
     case MR_OPT_PEER_TIMEOUT_S:
       return guarded([&]() { return ctx->eng.set_peer_timeout(value); });
+    case MR_OPT_SOLVE_BLOCKED:
+      MR_CHECK(value == 0.0 || value == 1.0, "solve_blocked must be 0 or 1");
+      ctx->eng.solve_blocked = value == 1.0;
+      return 0;
+    case MR_OPT_SOLVE_SLOTS:
+      MR_CHECK(value >= 0.0 && value <= 4096.0 && value == (double)(int)value,
+               "solve_slots must be an integer in [0, 4096]");
+      ctx->eng.solve_slots = (int)value;
+      return 0;
     default: MR_CHECK(false, "unknown option");
   }
 }

@@ -99,6 +99,14 @@ struct Engine {
   // MR_SOLVER_NNLS (mr_als_set_nnls; nnls.hip): round cap (0: 4 (k + 1)) and start
   int nnls_max_rounds = 0;
   bool nnls_warm = true;
+  // MR_SOLVER_CHOLESKY by the blocked kernel (cholesky.hip; MR_OPT_SOLVE_BLOCKED),
+  // its forced slot count (MR_OPT_SOLVE_SLOTS; 0: automatic) and its scratch,
+  // allocated at the first blocked solve and grown when a side needs more
+  bool solve_blocked = false;
+  int solve_slots = 0;
+  double* d_solve = nullptr;
+  int64_t solve_bytes = 0;
+  int solve_cus = 0;
   int chunk = 2048;
   // ridge on the k factor coordinates of both sides (mr_als_set_regularization):
   // G_e += reg_lambda w_e I_k after every Gram, w_e = 1 or the rating count
@@ -213,6 +221,8 @@ struct Engine {
                  Inflight* deferred = nullptr);
   CgStart cg_start_of(Side& S);
   int solve(Side& S);
+  // the blocked kernel's scratch for this side: *slots slots in d_solve
+  int solve_scratch(const Side& S, int* slots);
   int solve_nnls(Side& S);
   // the side's last NNLS solve: per-entity rounds (rounds may be NULL) and
   // {entities, sum of rounds, max rounds, unconverged} (out4 may be NULL)

@@ -78,6 +78,7 @@ Engine::~Engine() {
     dfree(d_state, stream); dfree(partials, stream); dfree(d_flag, stream); dfree(xbins, stream);
     dfree(d_resgen, stream); dfree(d_resctl, stream);
     dfree(S16, stream); dfree(yty_part, stream);
+    dfree(d_solve, stream);
     dfree(d_peer, stream);
     for (void* q : peer_opened) (void)hipIpcCloseMemHandle(q);
     if (peer_buf) (void)hipFree(peer_buf);
@@ -1382,11 +1383,16 @@ int Engine::solve(Side& S) {
   if (solver == MR_SOLVER_NNLS) return solve_nnls(S);
   float *xf, *xb;
   x_ptrs(S, &xf, &xb);
+  int slots = 0;
+  if (solve_blocked && solve_scratch(S, &slots)) return -1;
   MR_HIP(hipMemsetAsync(d_flag, 0, 4, stream));
   hipEvent_t a = nullptr;
   if (tic(MR_K_SOLVE, -1, &a)) return -1;
-  if (launch_solve(stream, S.user, S.E, k, ridge, S.G, S.Gs, S.Gn, S.C, S.Cb, xf, xb,
-                   d_flag))
+  if (solve_blocked
+          ? launch_solve_blocked(stream, S.user, S.E, k, ridge, S.G, S.Gs, S.Gn, S.C, S.Cb, xf,
+                                 xb, d_flag, d_solve, slots)
+          : launch_solve(stream, S.user, S.E, k, ridge, S.G, S.Gs, S.Gn, S.C, S.Cb, xf, xb,
+                         d_flag))
     return -1;
   if (toc(MR_K_SOLVE, -1, a)) return -1;
   int bad = 0;
@@ -1394,6 +1400,35 @@ int Engine::solve(Side& S) {
   MR_HIP(hipStreamSynchronize(stream));
   if (S.user) stats.nonpd_users += bad;
   else stats.nonpd_items += bad;
+  return 0;
+}
+
+// Slots of the blocked solve (cholesky.hip) for this side -- the forced
+// count, or min(E, 2 x CUs, 256 MiB / slot) -- and a scratch that holds them.
+// Every solve ends with a stream synchronisation, so no kernel is using the
+// scratch when a larger one replaces it.
+int Engine::solve_scratch(const Side& S, int* slots) {
+  MR_CHECK(k >= 1 && k <= kMaxKLarge, "the blocked exact solver runs 1 <= k <= 512");
+  const int64_t per = solve_slot_bytes(S.user ? k + 1 : k);
+  if (!solve_cus)
+    MR_HIP(hipDeviceGetAttribute(&solve_cus, hipDeviceAttributeMultiprocessorCount, device));
+  int64_t n = solve_slots > 0 ? std::min<int64_t>(S.E, solve_slots)
+                              : std::min<int64_t>({S.E, 2 * (int64_t)solve_cus,
+                                                   (int64_t(256) << 20) / per});
+  n = std::max<int64_t>(n, 1);
+  if (n * per > solve_bytes) {
+    if (d_solve) (void)hipFree(d_solve);
+    d_solve = nullptr;
+    solve_bytes = 0;
+    if (hipMalloc((void**)&d_solve, (size_t)(n * per)) != hipSuccess) {
+      (void)hipGetLastError();
+      d_solve = nullptr;
+      MR_CHECK(false, "the blocked exact solver could not allocate its scratch (" +
+                          std::to_string(n) + " slots of " + std::to_string(per) + " bytes)");
+    }
+    solve_bytes = n * per;
+  }
+  *slots = (int)n;
   return 0;
 }
 

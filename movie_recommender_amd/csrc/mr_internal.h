@@ -117,9 +117,8 @@ __host__ __device__ inline int off_index(int bi, int bj, int nb) {
 // for k = 64): virtual v = 16*b + i  <->  natural n = NB*i + b.
 __host__ __device__ inline int virt_of(int n, int nb) { return 16 * (n % nb) + n / nb; }
 __host__ __device__ inline int nat_of(int v, int nb) { return nb * (v & 15) + (v >> 4); }
-// Offset of natural element (i, j) of a tri16 G_e.
-__host__ __device__ inline int64_t packed_offset(int i, int j, int nb) {
-  int vi = virt_of(i, nb), vj = virt_of(j, nb);
+// Offset of virtual element (vi, vj) of a tri16 G_e.
+__host__ __device__ inline int64_t packed_offset_virt(int vi, int vj, int nb) {
   if ((vi >> 4) > (vj >> 4) || ((vi >> 4) == (vj >> 4) && (vi & 15) > (vj & 15))) {
     const int t = vi; vi = vj; vj = t;      // symmetric: use (min, max)
   }
@@ -131,6 +130,10 @@ __host__ __device__ inline int64_t packed_offset(int i, int j, int nb) {
   if ((bi & 1) == 0) return (int64_t)(base + m) * 256 + ri * 16 + rj;       // upper incl. diag
   if (ri == rj) return (int64_t)n_tiles_of(nb) * 256 + m * 16 + ri;         // side array
   return (int64_t)(base + m) * 256 + rj * 16 + ri;                          // strict lower
+}
+// Offset of natural element (i, j) of a tri16 G_e.
+__host__ __device__ inline int64_t packed_offset(int i, int j, int nb) {
+  return packed_offset_virt(virt_of(i, nb), virt_of(j, nb), nb);
 }
 
 // One wave's unit of Gram work: ratings [begin, begin+len) of one entity's
@@ -381,6 +384,15 @@ int launch_solve(hipStream_t s, bool user_side, int64_t E, int k, double ridge,
                  const float* G, const float* Gs, const float* Gn,
                  const float* C, const float* Cb, float* x, float* xb,
                  int* nonpd);
+// cholesky.hip: the same solve (operands and results of launch_solve) by a
+// tiled factorisation on the fp64 matrix instruction, 1 <= k <= 512.  One
+// workgroup per scratch slot of solve_slot_bytes(K) bytes (K = k + 1 on the
+// user side), min(E, slots) of them; scratch holds `slots` slots.
+int64_t solve_slot_bytes(int K);
+int launch_solve_blocked(hipStream_t s, bool user_side, int64_t E, int k, double ridge,
+                         const float* G, const float* Gs, const float* Gn, const float* C,
+                         const float* Cb, float* x, float* xb, int* nonpd, double* scratch,
+                         int slots);
 // nnls.hip: per-entity non-negative solve by block principal pivoting (same
 // operands as launch_solve; rounds[E] gets the rounds used: > 0 converged,
 // < 0 stopped at the cap, 0 not positive definite and counted in *nonpd).

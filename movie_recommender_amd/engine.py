@@ -14,7 +14,8 @@ from . import _lib
 SOLVERS = {"cg": 0, "cholesky": 1, "nnls": 2}   # MR_SOLVER_* of include/mr_als.h
 OPTIONS = {"fuse_start": 0, "cg_speculate": 1, "wait_timeout_s": 2,
            "cg_onepass": 3, "gram_rhs_mfma": 4, "cg_sweep": 5,
-           "peer_timeout_s": 6, "cg_tile_nt": 7, "cg_resident": 8}   # include/mr_als.h
+           "peer_timeout_s": 6, "cg_tile_nt": 7, "cg_resident": 8,
+           "solve_blocked": 9, "solve_slots": 10}   # include/mr_als.h
 REG_MODES = {"constant": 0, "weighted": 1}   # MR_REG_* of include/mr_als.h
 
 
@@ -193,8 +194,10 @@ class AlsContext:
         self.implicit_alpha = alpha
 
     def set_option(self, name, value):
-        """Engine option (``mr_als_set_option``): ``fuse_start``,
-        ``cg_speculate`` (0/1) or ``wait_timeout_s``."""
+        """Engine option (``mr_als_set_option``), a key of ``OPTIONS``: e.g.
+        ``fuse_start``, ``cg_speculate``, ``wait_timeout_s``, or
+        ``solve_blocked`` (1: ``solver="cholesky"`` half-steps run the blocked
+        kernel, every k <= 512; 0, the default: K x K in LDS, k <= 128)."""
         _lib.check(_lib.lib().mr_als_set_option(self._h, OPTIONS[name], float(value)),
                    "mr_als_set_option")
 
