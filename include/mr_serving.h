@@ -46,6 +46,14 @@ mr_rec* mr_rec_create(int device, int k, int n_als, const double* als_movie_fact
 void mr_rec_destroy(mr_rec* ctx);
 int mr_rec_num_candidates(const mr_rec* ctx);
 
+/* Users per device pass of mr_rec_scores and mr_rec_top_n.  A call with more
+ * users goes through the device in consecutive chunks of this many (model
+ * rows, exclusion lists and output rows follow the chunk; the results do not
+ * depend on it).  The rule: as many users as keep one chunk's score / key
+ * scratch (n_cand * 8 bytes per user) within 1 GiB, at most 65,535 * 32 (the
+ * score grid) and at least 32.  Read-only; -1 for a NULL table. */
+long long mr_rec_user_chunk(const mr_rec* ctx);
+
 /* Fold-in of n_users rating lists (models.py:676-697): user u's rows are
  * off[u] .. off[u+1]-1, each an ALS movie id and the RAW rating (median not
  * subtracted, as in the reference).  The caller applies the reference's

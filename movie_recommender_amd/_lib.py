@@ -190,6 +190,7 @@ SIGNATURES = {
                            DP]),
     "mr_rec_destroy": (None, [VP]),
     "mr_rec_num_candidates": (ctypes.c_int, [VP]),
+    "mr_rec_user_chunk": (ctypes.c_longlong, [VP]),
     "mr_rec_fold_in": (ctypes.c_int, [VP, ctypes.c_int, LLP, IP, DP, DP, IP]),
     "mr_rec_scores": (ctypes.c_int, [VP, ctypes.c_int, DP, DP]),
     "mr_rec_top_n": (ctypes.c_int, [VP, ctypes.c_int, DP, LLP, IP, ctypes.c_int, IP, DP, IP]),

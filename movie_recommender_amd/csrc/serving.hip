@@ -1149,6 +1149,8 @@ void mr_rec_destroy(mr_rec* ctx) { delete ctx; }
 
 int mr_rec_num_candidates(const mr_rec* ctx) { return ctx ? ctx->r.n_cand : -1; }
 
+long long mr_rec_user_chunk(const mr_rec* ctx) { return ctx ? mr::user_chunk(&ctx->r) : -1; }
+
 int mr_rec_fold_in(mr_rec* ctx, int n_users, const long long* off, const int* als_idx,
                    const double* ratings, double* x_out, int* method_out) {
   if (!ctx) return -1;

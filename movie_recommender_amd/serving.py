@@ -62,15 +62,20 @@ class MovieTable:
         self.cand_als = np.array([c[1] for c in cand], np.int32)
         self.cand_med = np.array([c[2] for c in cand], np.float64)
         self.cand_index = {int(m): c for c, m in enumerate(self.cand_mid)}
-        # movie id -> candidate index (-1: not a candidate), for array inputs
-        self._cand_lut = np.full(int(self.cand_mid.max()) + 1 if len(cand) else 1, -1, np.int32)
-        self._cand_lut[self.cand_mid] = np.arange(len(cand), dtype=np.int32)
+        self._index_ids()
         L = _lib.lib()
         self._h = L.mr_rec_create(int(device), self.k, self.n_als, _dp(V), len(cand),
                                   _ip(self.cand_als), _ip(self.cand_mid), _dp(self.cand_med))
         if not self._h:
             raise RuntimeError("mr_rec_create failed: " + _lib.last_error())
         self._V = V
+
+    def _index_ids(self):
+        """Movie id -> candidate index for array inputs: the ids sorted, with
+        their candidate indices (memory by the number of candidates, not by
+        the largest id -- a table indexed by id is 8 GiB at ids near 2^31)."""
+        self._mid_order = np.argsort(self.cand_mid, kind="stable").astype(np.int32)
+        self._mid_sorted = self.cand_mid[self._mid_order].astype(np.int64)
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
@@ -93,6 +98,15 @@ class MovieTable:
     @property
     def num_candidates(self):
         return len(self.cand_mid)
+
+    @property
+    def user_chunk(self):
+        """Users per device pass of ``scores`` / ``top_n``; larger batches go
+        through in chunks of this many (``mr_rec_user_chunk``)."""
+        n = int(_lib.lib().mr_rec_user_chunk(self._h))
+        if n < 1:
+            raise RuntimeError("mr_rec_user_chunk failed")
+        return n
 
     def kernel_ms(self):
         ms = np.zeros(6)
@@ -268,9 +282,11 @@ class MovieTable:
         container path does), vectorised."""
         if off.shape != (B + 1,) or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != len(mids):
             raise ValueError("rated offsets must be int64[B + 1], non-decreasing, from 0 to len(ids)")
-        ok = (mids >= 0) & (mids < len(self._cand_lut))
         c = np.full(len(mids), -1, np.int32)
-        c[ok] = self._cand_lut[mids[ok]]
+        if len(self._mid_sorted):
+            p = np.minimum(np.searchsorted(self._mid_sorted, mids), len(self._mid_sorted) - 1)
+            hit = self._mid_sorted[p] == mids
+            c[hit] = self._mid_order[p[hit]]
         keep = c >= 0
         kept = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
         excl_off = np.ascontiguousarray(kept[off], np.int64)

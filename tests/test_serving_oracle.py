@@ -77,8 +77,7 @@ def test_exclusion_csr_matches_container_path():
     rs = np.random.RandomState(3)
     t.cand_mid = np.sort(rs.choice(5000, 800, replace=False)).astype(np.int32)
     t.cand_index = {int(m): c for c, m in enumerate(t.cand_mid)}
-    t._cand_lut = np.full(int(t.cand_mid.max()) + 1, -1, np.int32)
-    t._cand_lut[t.cand_mid] = np.arange(len(t.cand_mid), dtype=np.int32)
+    t._index_ids()
     lists = [rs.choice(6000, rs.randint(0, 40), replace=False) for _ in range(50)] + [[]]
     off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
     ids = np.concatenate([np.asarray(l, np.int64) for l in lists] + [np.array([-5], np.int64)])
