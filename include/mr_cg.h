@@ -56,6 +56,12 @@ int mr_cg_solve(mr_cg* ctx, const double* b, double* x, double min_r_decrease,
                 int max_iteration, double* final_rr);
 
 int mr_cg_set_timing(mr_cg* ctx, int enable);
+/* How the SpMVs load the gathered vector.  0 (default): by size -- buffer
+ * loads while the vector is below 4 GiB, 64-bit pointer loads from there on.
+ * 1: pointer loads at any size (the same products and sums in the same
+ * order, so the same bits; for tests of the path a 4 GiB vector takes).
+ * Holds for the context's later solves. */
+int mr_cg_set_gather_path(mr_cg* ctx, int mode);
 int mr_cg_get_stats(mr_cg* ctx, mr_cg_stats* out);
 int mr_cg_reset_stats(mr_cg* ctx);
 

@@ -183,6 +183,7 @@ SIGNATURES = {
     "mr_cg_destroy": (None, [VP]),
     "mr_cg_solve": (ctypes.c_int, [VP, DP, DP, ctypes.c_double, ctypes.c_int, DP]),
     "mr_cg_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
+    "mr_cg_set_gather_path": (ctypes.c_int, [VP, ctypes.c_int]),
     "mr_cg_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(MrCgStats)]),
     "mr_cg_reset_stats": (ctypes.c_int, [VP]),
     # factor consumers (include/mr_serving.h)

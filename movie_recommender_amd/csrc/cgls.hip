@@ -70,6 +70,7 @@ struct CgLs {
   CgMirror *h_mirror = nullptr, *d_mirror = nullptr;
   int seq = 0;
   bool timing = false;
+  bool ptr_loads = false;   // mr_cg_set_gather_path: the SpMVs' pointer-load twins
   struct Timed {
     int cls, it;
     hipEvent_t a, b;
@@ -141,13 +142,15 @@ struct CgLs {
     int64_t* rp0 = nullptr;
     double* v0 = nullptr;
     // ids / values padded by kSpPad entries: the SpMV's 16-byte row-block
-    // loads may run up to 7 entries past a block's (and the array's) end
+    // loads may run up to 7 entries past a block's (and the array's) end;
+    // rp2 holds one (r, p) pair at least: the pointer-load SpMV gathers pair 0
+    // for the lanes past a block's entries (cols = 0: blocks of empty rows)
     if (dmalloc(&rp, rows + 1, owned) || dmalloc(&ci, nnz + kSpPad, owned) ||
         dmalloc(&v, nnz + kSpPad, owned) ||
         dmalloc(&perm, rows, owned) || dmalloc(&tp, cols + 1, owned) ||
         dmalloc(&ti, nnz + kSpPad, owned) || dmalloc(&tv, nnz + kSpPad, owned) || dmalloc(&b_in, rows, owned) ||
         dmalloc(&b, rows, owned) || dmalloc(&t, rows, owned) || dmalloc(&b2, cols, owned) ||
-        dmalloc(&x, cols, owned) || dmalloc(&rp2, 2 * cols, owned) ||
+        dmalloc(&x, cols, owned) || dmalloc(&rp2, 2 * std::max<int64_t>(cols, 1), owned) ||
         dmalloc(&q, cols, owned) || dmalloc(&partials, kMaxParts, owned) ||
         dmalloc(&st, 1, owned))
       return -1;
@@ -222,12 +225,12 @@ struct CgLs {
     if (tic(MR_CG_K_SPMV_A, it) ||
         launch_csr_spmv(s, it > 0 ? SPG_P : SPG_P0, SPO_STORE, st, n_blk_a, blk_a, rp, ci, v,
                         rp2, nullptr, 2 * cols, t, nullptr, nullptr, 0, nullptr, kMaxParts,
-                        nullptr) ||
+                        nullptr, ptr_loads) ||
         toc())
       return -1;
     if (tic(MR_CG_K_SPMV_AT, it) ||
         launch_csr_spmv(s, SPG_X, SPO_CG, st, n_blk_t, blk_t, tp, ti, tv, t, nullptr, rows, q, rp2, nullptr,
-                        it > 0 ? 1 : 0, partials, kMaxParts, st) ||
+                        it > 0 ? 1 : 0, partials, kMaxParts, st, ptr_loads) ||
         toc())
       return -1;
     if (tic(MR_CG_K_UPDATE, it) ||
@@ -258,11 +261,11 @@ struct CgLs {
     // b2 = A^T b (:463); r0 = A^T (A x) - b2, p0 = -r0, rr (:466-485)
     if (tic(MR_CG_K_SETUP, -1) ||
         launch_csr_spmv(s, SPG_X, SPO_STORE, nullptr, n_blk_t, blk_t, tp, ti, tv, b, nullptr,
-                        rows, b2, nullptr, nullptr, 0, nullptr, kMaxParts, nullptr) ||
+                        rows, b2, nullptr, nullptr, 0, nullptr, kMaxParts, nullptr, ptr_loads) ||
         launch_csr_spmv(s, SPG_X, SPO_STORE, nullptr, n_blk_a, blk_a, rp, ci, v, x, nullptr, cols, t,
-                        nullptr, nullptr, 0, nullptr, kMaxParts, nullptr) ||
+                        nullptr, nullptr, 0, nullptr, kMaxParts, nullptr, ptr_loads) ||
         launch_csr_spmv(s, SPG_X, SPO_STORE, nullptr, n_blk_t, blk_t, tp, ti, tv, t, nullptr, rows, q,
-                        nullptr, nullptr, 0, nullptr, kMaxParts, nullptr) ||
+                        nullptr, nullptr, 0, nullptr, kMaxParts, nullptr, ptr_loads) ||
         launch_cgls_update(s, st, UPD_INIT, cols, x, rp2, q, b2, partials, kUpdParts, st,
                            d_mirror, ++seq) ||
         toc())
@@ -371,6 +374,13 @@ int mr_cg_solve(mr_cg* ctx, const double* b, double* x, double min_r_decrease, i
 int mr_cg_set_timing(mr_cg* ctx, int enable) {
   MR_CHECK(ctx, "null context");
   ctx->c.timing = enable != 0;
+  return 0;
+}
+
+int mr_cg_set_gather_path(mr_cg* ctx, int mode) {
+  MR_CHECK(ctx, "null context");
+  MR_CHECK(mode == 0 || mode == 1, "gather path: 0 (by size) or 1 (pointer loads)");
+  ctx->c.ptr_loads = mode == 1;
   return 0;
 }
 

@@ -4898,7 +4898,7 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
                     const int64_t* blk, const int64_t* rp, const int32_t* ci, const double* v,
                     const double* xa, const double* xb, int64_t nx, double* out, double* pv,
                     const double* rv, int update_p, double* partials, int n_part,
-                    CgState* fst) {
+                    CgState* fst, bool ptr_loads) {
   if (n_blk <= 0) return 0;
   // at most the workgroups the chip holds at once: a fixed grid larger than
   // that runs a second, partial round of grid-stride loops (general CG at
@@ -4910,7 +4910,7 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
       return 0;
     return n;
   }();
-  const bool buf = nx >= 0 && nx * 8 < (int64_t)0xFFFFFFF0;
+  const bool buf = !ptr_loads && nx >= 0 && nx * 8 < (int64_t)0xFFFFFFF0;
   const void* fn = nullptr;
 #define MR_SP_FN(GA, OU)                                                                   \
   fn = buf ? (const void*)csr_spmv_kernel<GA, OU, true> : (const void*)csr_spmv_kernel<GA, OU, false>

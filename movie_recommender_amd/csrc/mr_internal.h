@@ -439,7 +439,9 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
                     const int64_t* blk, const int64_t* rp, const int32_t* ci, const double* v,
                     const double* xa, const double* xb, int64_t nx, double* out, double* pv,
                     const double* rv, int update_p, double* partials, int n_part,
-                    CgState* fst);   // nx: length of the gathered vector(s) xa / xb
+                    CgState* fst, bool ptr_loads = false);
+// nx: length of the gathered vector(s) xa / xb; ptr_loads: the pointer-load
+// twin even where nx would allow buffer loads (mr_cg_set_gather_path)
 int launch_cgls_update(hipStream_t s, const CgState* st, int mode, int64_t n, double* x,
                        double* rp, const double* q, const double* b2,
                        double* partials, int n_part, CgState* fst, CgMirror* mirror, int seq);

@@ -8,7 +8,7 @@ import pytest
 
 from conftest import ROOT
 
-HEADERS = [os.path.join(ROOT, "include", h) for h in ("cpp_ls_lib.h", "mr_als.h", "mr_serving.h", "mr_prep.h", "mr_similar.h")]
+HEADERS = [os.path.join(ROOT, "include", h) for h in ("cpp_ls_lib.h", "mr_als.h", "mr_serving.h", "mr_prep.h", "mr_similar.h", "mr_cg.h")]
 
 
 def declared_functions():
