@@ -1,0 +1,89 @@
+/*
+ * mr_lsqr.h -- device-resident general sparse LSQR (Paige & Saunders) for
+ * MI355X (gfx950): min ||A x - b||^2 + damp^2 ||x - x0||^2 on A itself, with
+ * SciPy's stopping rules and norm estimates.
+ *
+ * The reference's SciPy ALS (python/100k_data/ratings_als.py:347-529) runs
+ * scipy.sparse.linalg.lsqr on a global design matrix per half-step.  A
+ * context here uploads A's structure once (rows ordered by first column, the
+ * explicit transpose and the CSR-stream row blocks built on the device, as
+ * mr_cg does), takes new values without a re-sort, and solves with three
+ * kernels per iteration and no host round trip.  The solver restates
+ * scipy/sparse/linalg/_isolve/lsqr.py (1.15) operation for operation;
+ * calc_var and show are not offered.
+ *
+ * Limit: every norm is the sqrt of a plain fp64 sum of squares (no scaling
+ * against overflow), so entries beyond ~1e154 overflow where BLAS nrm2 would
+ * not.
+ */
+#ifndef MR_LSQR_H
+#define MR_LSQR_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mr_lsqr mr_lsqr;
+
+/* Kernel classes timed with HIP events when timing is enabled. */
+enum {
+  MR_LSQR_K_A = 0,   /* uh = A v - alfa u, sum uh^2; beta, anorm                   */
+  MR_LSQR_K_AT,      /* vh = A^T u - beta v, sum vh^2; alfa, rotations, norms      */
+  MR_LSQR_K_X,       /* dk, x, w updates, sum dk^2; ddnorm, stop tests, publish    */
+  MR_LSQR_K_SETUP,   /* u = b - A x0, v = A^T u, w = v (per solve)                 */
+  MR_LSQR_K_COUNT
+};
+
+typedef struct mr_lsqr_result {
+  int istop, itn;
+  double r1norm, r2norm, anorm, acond, arnorm, xnorm;
+} mr_lsqr_result;
+
+typedef struct mr_lsqr_stats {
+  int last_iterations;            /* itn of the last solve                        */
+  long long iterations_total;     /* over all solves since the last reset         */
+  double solve_ms;                /* device time of the solves (setup .. stop)    */
+  double kernel_ms[MR_LSQR_K_COUNT];
+  long long kernel_launches[MR_LSQR_K_COUNT];  /* launches that did work         */
+  long long rows, cols, nnz;
+  long long blocks_a, blocks_at;  /* CSR-stream row blocks of A and of A^T        */
+  long long block_max_nnz, block_max_rows;
+} mr_lsqr_stats;
+
+/* A in CSR form as mr_cg_create takes it: row_indices[rows+1] (int32, from 0,
+ * non-decreasing), col_indices / values [row_indices[rows]]; duplicate and
+ * unsorted column ids within a row are legal.  NULL on error (mr_last_error). */
+mr_lsqr* mr_lsqr_create(int device, int rows, int cols, const int* row_indices,
+                        const int* col_indices, const double* values);
+void mr_lsqr_destroy(mr_lsqr* ctx);
+
+/* The same structure with new values, given in the caller's CSR order; the
+ * device applies the stored row-sort and transpose maps. */
+int mr_lsqr_set_values(mr_lsqr* ctx, const double* values);
+/* index[nnz], stored once: -1 = the constant 1.0, any other entry (>= 0) an
+ * index into the table of a later mr_lsqr_set_values_from_table. */
+int mr_lsqr_set_value_map(mr_lsqr* ctx, const int* index);
+/* values[j] = index[j] < 0 ? 1.0 : table[index[j]], gathered on the device. */
+int mr_lsqr_set_values_from_table(mr_lsqr* ctx, const double* table, long long table_len);
+
+/* scipy.sparse.linalg.lsqr(A, b, damp, atol, btol, conlim, iter_lim, x0=x0):
+ * b[rows]; x0_or_null[cols] (NULL: x0 = 0); x_out[cols]; *out as SciPy's
+ * istop, itn, r1norm, r2norm, anorm, acond, arnorm, xnorm.  0, or < 0 on
+ * error. */
+int mr_lsqr_solve(mr_lsqr* ctx, const double* b, const double* x0_or_null, double damp,
+                  double atol, double btol, double conlim, int iter_lim, double* x_out,
+                  mr_lsqr_result* out);
+/* *out = sum_i |b_i - (A x)_i|, one pass over A. */
+int mr_lsqr_residual_l1(mr_lsqr* ctx, const double* b, const double* x, double* out);
+
+int mr_lsqr_set_timing(mr_lsqr* ctx, int enable);
+/* 0 (default): buffer loads while the gathered vector is below 4 GiB; 1:
+ * pointer loads at any size (the same bits), as mr_cg_set_gather_path. */
+int mr_lsqr_set_gather_path(mr_lsqr* ctx, int mode);
+int mr_lsqr_get_stats(mr_lsqr* ctx, mr_lsqr_stats* out);
+int mr_lsqr_reset_stats(mr_lsqr* ctx);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MR_LSQR_H */

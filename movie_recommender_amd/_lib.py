@@ -3,7 +3,8 @@
 The shared library exports the reference ABI (``include/cpp_ls_lib.h``), the
 device-resident engine API (``include/mr_als.h``), the factor consumers
 (``include/mr_serving.h``), the general sparse least squares
-(``include/mr_cg.h``), the training-set preparation
+(``include/mr_cg.h``), the general sparse LSQR (``include/mr_lsqr.h``),
+the training-set preparation
 (``include/mr_prep.h``), the similar-movies database
 (``include/mr_similar.h``), the ranking evaluation / implicit fold-in
 (``include/mr_ranking.h``), the general fold-in
@@ -88,6 +89,38 @@ class MrCgStats(ctypes.Structure):
                 "rows": self.rows, "cols": self.cols, "nnz": self.nnz,
                 "blocks_a": self.blocks_a, "blocks_at": self.blocks_at,
                 "block_max_nnz": self.block_max_nnz, "block_max_rows": self.block_max_rows}
+
+
+LSQR_K_NAMES = ["ka", "kt", "kx", "setup"]
+
+
+class MrLsqrStats(ctypes.Structure):
+    _fields_ = [("last_iterations", ctypes.c_int),
+                ("iterations_total", ctypes.c_longlong),
+                ("solve_ms", ctypes.c_double),
+                ("kernel_ms", ctypes.c_double * len(LSQR_K_NAMES)),
+                ("kernel_launches", ctypes.c_longlong * len(LSQR_K_NAMES)),
+                ("rows", ctypes.c_longlong), ("cols", ctypes.c_longlong),
+                ("nnz", ctypes.c_longlong),
+                ("blocks_a", ctypes.c_longlong), ("blocks_at", ctypes.c_longlong),
+                ("block_max_nnz", ctypes.c_longlong), ("block_max_rows", ctypes.c_longlong)]
+
+    def as_dict(self):
+        return {"last_iterations": self.last_iterations,
+                "iterations_total": self.iterations_total, "solve_ms": self.solve_ms,
+                "kernel_ms": {n: self.kernel_ms[i] for i, n in enumerate(LSQR_K_NAMES)},
+                "kernel_launches": {n: self.kernel_launches[i]
+                                    for i, n in enumerate(LSQR_K_NAMES)},
+                "rows": self.rows, "cols": self.cols, "nnz": self.nnz,
+                "blocks_a": self.blocks_a, "blocks_at": self.blocks_at,
+                "block_max_nnz": self.block_max_nnz, "block_max_rows": self.block_max_rows}
+
+
+class MrLsqrResult(ctypes.Structure):
+    _fields_ = [("istop", ctypes.c_int), ("itn", ctypes.c_int),
+                ("r1norm", ctypes.c_double), ("r2norm", ctypes.c_double),
+                ("anorm", ctypes.c_double), ("acond", ctypes.c_double),
+                ("arnorm", ctypes.c_double), ("xnorm", ctypes.c_double)]
 
 
 class MrComm(ctypes.Structure):
@@ -186,6 +219,20 @@ SIGNATURES = {
     "mr_cg_set_gather_path": (ctypes.c_int, [VP, ctypes.c_int]),
     "mr_cg_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(MrCgStats)]),
     "mr_cg_reset_stats": (ctypes.c_int, [VP]),
+    # general sparse LSQR (include/mr_lsqr.h)
+    "mr_lsqr_create": (VP, [ctypes.c_int, ctypes.c_int, ctypes.c_int, IP, IP, DP]),
+    "mr_lsqr_destroy": (None, [VP]),
+    "mr_lsqr_set_values": (ctypes.c_int, [VP, DP]),
+    "mr_lsqr_set_value_map": (ctypes.c_int, [VP, IP]),
+    "mr_lsqr_set_values_from_table": (ctypes.c_int, [VP, DP, ctypes.c_longlong]),
+    "mr_lsqr_solve": (ctypes.c_int, [VP, DP, DP, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_int, DP,
+                                     ctypes.POINTER(MrLsqrResult)]),
+    "mr_lsqr_residual_l1": (ctypes.c_int, [VP, DP, DP, DP]),
+    "mr_lsqr_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
+    "mr_lsqr_set_gather_path": (ctypes.c_int, [VP, ctypes.c_int]),
+    "mr_lsqr_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(MrLsqrStats)]),
+    "mr_lsqr_reset_stats": (ctypes.c_int, [VP]),
     # factor consumers (include/mr_serving.h)
     "mr_rec_create": (VP, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP, ctypes.c_int, IP, IP,
                            DP]),

@@ -19,6 +19,7 @@
 
 #include "../../include/mr_cg.h"
 #include "engine.h"
+#include "sp_structure.h"
 
 namespace mr {
 
@@ -43,17 +44,93 @@ std::vector<int64_t> row_blocks(const std::vector<int64_t>& off) {
   return blk;
 }
 
-template <typename T>
-int dmalloc(T** p, int64_t n, std::vector<void*>& owned) {
-  *p = nullptr;
-  MR_HIP(hipMalloc((void**)p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
-  owned.push_back(*p);
+}  // namespace
+
+int SpStructure::check(int rows_, int cols_, const int* hrp, const int* hci, const double* hv) {
+  MR_CHECK(rows_ >= 0 && cols_ >= 0, "negative matrix dimension");
+  MR_CHECK(hrp && hrp[0] == 0, "row indices must start at 0");
+  for (int i = 0; i < rows_; ++i) MR_CHECK(hrp[i + 1] >= hrp[i], "row indices not monotone");
+  MR_CHECK((hci && hv) || hrp[rows_] == 0, "null column indices or values");
+  const int64_t n = hrp[rows_];
+  for (int64_t j = 0; j < n; ++j)
+    MR_CHECK(hci[j] >= 0 && hci[j] < cols_, "column index out of range");
   return 0;
 }
 
-}  // namespace
+int SpStructure::build(hipStream_t s, int rows_, int cols_, const int* hrp, const int* hci,
+                       const double* hv, std::vector<void*>& owned) {
+  rows = rows_;
+  cols = cols_;
+  nnz = hrp[rows_];
+  int32_t *rp32 = nullptr, *rowof = nullptr, *ci0 = nullptr;
+  int64_t* rp0 = nullptr;
+  double* v0 = nullptr;
+  // ids / values padded by kSpPad entries: the SpMV's 16-byte row-block
+  // loads may run up to 7 entries past a block's (and the array's) end
+  if (sp_dmalloc(&rp, rows + 1, owned) || sp_dmalloc(&ci, nnz + kSpPad, owned) ||
+      sp_dmalloc(&v, nnz + kSpPad, owned) || sp_dmalloc(&perm, rows, owned) ||
+      sp_dmalloc(&tp, cols + 1, owned) || sp_dmalloc(&ti, nnz + kSpPad, owned) ||
+      sp_dmalloc(&tv, nnz + kSpPad, owned))
+    return -1;
+  std::vector<void*> tmp;
+  struct TmpFree {
+    std::vector<void*>& v;
+    hipStream_t s;
+    ~TmpFree() {
+      (void)hipStreamSynchronize(s);
+      for (void* q_ : v) (void)hipFree(q_);
+    }
+  } tmp_free{tmp, s};
+  if (sp_dmalloc(&rp32, rows + 1, tmp) || sp_dmalloc(&rp0, rows + 1, tmp) ||
+      sp_dmalloc(&ci0, nnz, tmp) || sp_dmalloc(&v0, nnz, tmp))
+    return -1;
+  MR_H2D(rp32, hrp, (rows + 1) * 4, s);
+  if (nnz) {
+    MR_H2D(ci0, hci, nnz * 4, s);
+    MR_H2D(v0, hv, nnz * 8, s);
+  }
+  if (launch_i32_to_i64(s, rows + 1, rp32, rp0)) return -1;
+  // rows ordered by first column (a row permutation: same solution, same
+  // row sums), so A^T's rows read t in runs and A's rows gather r, p from
+  // neighbouring columns (csr_build.hip sort_rows_by_first_col)
+  if (sort_rows_by_first_col(s, rows, cols, rp0, ci0, v0, perm, rp, ci, v)) return -1;
+  for (void* q_ : {(void*)rp32, (void*)rp0, (void*)ci0, (void*)v0}) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(q_);
+  }
+  tmp.clear();
+  if (sp_dmalloc(&rowof, nnz, tmp)) return -1;
+  // explicit transpose (sparse_matrix_transpose, matrix.cpp:617-692): a
+  // stable sort of the non-zeros by column keeps each column's rows in order
+  if (launch_rows_of(s, rows, rp, rowof)) return -1;
+  if (build_csr<double, double>(s, nnz, cols, ci, 0, rowof, v, tp, ti, tv)) return -1;
+  // row blocks of A and of A^T (offsets read back once)
+  std::vector<int64_t> offa(rows + 1), offt(cols + 1);
+  MR_D2H(offa.data(), rp, (rows + 1) * 8, s);
+  MR_D2H(offt.data(), tp, (cols + 1) * 8, s);
+  // uploaded as (first row, its first non-zero) pairs: the kernels read a
+  // block's bounds with no dependent load through the row offsets
+  auto pairs = [](const std::vector<int64_t>& bl, const std::vector<int64_t>& off) {
+    std::vector<int64_t> pr(2 * bl.size());
+    for (size_t i = 0; i < bl.size(); ++i) {
+      pr[2 * i] = bl[i];
+      pr[2 * i + 1] = off[bl[i]];
+    }
+    return pr;
+  };
+  const std::vector<int64_t> ba = pairs(row_blocks(offa), offa),
+                             bt = pairs(row_blocks(offt), offt);
+  n_blk_a = (int64_t)ba.size() / 2 - 1;
+  n_blk_t = (int64_t)bt.size() / 2 - 1;
+  if (sp_dmalloc(&blk_a, (int64_t)ba.size(), owned) || sp_dmalloc(&blk_t, (int64_t)bt.size(), owned))
+    return -1;
+  MR_H2D(blk_a, ba.data(), ba.size() * 8, s);
+  MR_H2D(blk_t, bt.data(), bt.size() * 8, s);
+  MR_HIP(hipStreamSynchronize(s));
+  return 0;
+}
 
-struct CgLs {
+struct CgLs : LaunchTimer {
   int device = 0;
   hipStream_t s = nullptr;
   int64_t rows = 0, cols = 0, nnz = 0;
@@ -69,14 +146,7 @@ struct CgLs {
   CgState* h_init = nullptr;
   CgMirror *h_mirror = nullptr, *d_mirror = nullptr;
   int seq = 0;
-  bool timing = false;
   bool ptr_loads = false;   // mr_cg_set_gather_path: the SpMVs' pointer-load twins
-  struct Timed {
-    int cls, it;
-    hipEvent_t a, b;
-  };
-  std::vector<Timed> pend;
-  std::vector<hipEvent_t> pool;
   mr_cg_stats stats{};
 
   ~CgLs() {
@@ -86,51 +156,15 @@ struct CgLs {
     for (void* q_ : owned) (void)hipFree(q_);
     if (h_init) (void)hipHostFree(h_init);
     if (h_mirror) (void)hipHostFree(h_mirror);
-    for (auto& e : pool) (void)hipEventDestroy(e);
-    for (auto& e : pend) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+    destroy_events();
     (void)hipStreamDestroy(s);
   }
 
-  int ev(hipEvent_t* e) {
-    if (!pool.empty()) {
-      *e = pool.back();
-      pool.pop_back();
-      return 0;
-    }
-    MR_HIP(hipEventCreate(e));
-    return 0;
-  }
-  // a timed launch takes an event pair through the launch-timing slot
-  int tic(int cls, int it) {
-    if (!timing) return 0;
-    Timed tm{cls, it, nullptr, nullptr};
-    if (ev(&tm.a) || ev(&tm.b)) return -1;
-    t_launch.start = tm.a;
-    t_launch.stop = tm.b;
-    pend.push_back(tm);
-    return 0;
-  }
-  int toc() {
-    if (!timing) return 0;
-    if (t_launch.start) {   // nothing was launched: an empty interval
-      MR_HIP(hipEventRecord(pend.back().a, s));
-      MR_HIP(hipEventRecord(pend.back().b, s));
-    }
-    t_launch = LaunchTiming{};
-    return 0;
-  }
+  int toc() { return LaunchTimer::toc(s); }
 
   int init(int dev, int rows_, int cols_, const int* hrp, const int* hci, const double* hv) {
-    MR_CHECK(rows_ >= 0 && cols_ >= 0, "negative matrix dimension");
-    MR_CHECK(hrp && hrp[0] == 0, "row indices must start at 0");
-    for (int i = 0; i < rows_; ++i) MR_CHECK(hrp[i + 1] >= hrp[i], "row indices not monotone");
-    MR_CHECK((hci && hv) || hrp[rows_] == 0, "null column indices or values");
+    if (SpStructure::check(rows_, cols_, hrp, hci, hv)) return -1;
     device = dev;
-    rows = rows_;
-    cols = cols_;
-    nnz = hrp[rows_];
-    for (int64_t j = 0; j < nnz; ++j)
-      MR_CHECK(hci[j] >= 0 && hci[j] < cols_, "column index out of range");
     MR_HIP(hipSetDevice(device));
     MR_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     MR_HIP(hipHostMalloc((void**)&h_init, sizeof(CgState), hipHostMallocDefault));
@@ -138,77 +172,20 @@ struct CgLs {
                          hipHostMallocMapped | hipHostMallocCoherent));
     memset(h_mirror, 0, kMirrorSlots * sizeof(CgMirror));
     MR_HIP(hipHostGetDevicePointer((void**)&d_mirror, h_mirror, 0));
-    int32_t *rp32 = nullptr, *rowof = nullptr, *ci0 = nullptr;
-    int64_t* rp0 = nullptr;
-    double* v0 = nullptr;
-    // ids / values padded by kSpPad entries: the SpMV's 16-byte row-block
-    // loads may run up to 7 entries past a block's (and the array's) end;
+    SpStructure sp;
+    if (sp.build(s, rows_, cols_, hrp, hci, hv, owned)) return -1;
+    rows = sp.rows; cols = sp.cols; nnz = sp.nnz;
+    rp = sp.rp; tp = sp.tp; blk_a = sp.blk_a; blk_t = sp.blk_t;
+    n_blk_a = sp.n_blk_a; n_blk_t = sp.n_blk_t;
+    ci = sp.ci; ti = sp.ti; perm = sp.perm; v = sp.v; tv = sp.tv;
     // rp2 holds one (r, p) pair at least: the pointer-load SpMV gathers pair 0
     // for the lanes past a block's entries (cols = 0: blocks of empty rows)
-    if (dmalloc(&rp, rows + 1, owned) || dmalloc(&ci, nnz + kSpPad, owned) ||
-        dmalloc(&v, nnz + kSpPad, owned) ||
-        dmalloc(&perm, rows, owned) || dmalloc(&tp, cols + 1, owned) ||
-        dmalloc(&ti, nnz + kSpPad, owned) || dmalloc(&tv, nnz + kSpPad, owned) || dmalloc(&b_in, rows, owned) ||
-        dmalloc(&b, rows, owned) || dmalloc(&t, rows, owned) || dmalloc(&b2, cols, owned) ||
-        dmalloc(&x, cols, owned) || dmalloc(&rp2, 2 * std::max<int64_t>(cols, 1), owned) ||
-        dmalloc(&q, cols, owned) || dmalloc(&partials, kMaxParts, owned) ||
-        dmalloc(&st, 1, owned))
+    if (sp_dmalloc(&b_in, rows, owned) || sp_dmalloc(&b, rows, owned) ||
+        sp_dmalloc(&t, rows, owned) || sp_dmalloc(&b2, cols, owned) ||
+        sp_dmalloc(&x, cols, owned) || sp_dmalloc(&rp2, 2 * std::max<int64_t>(cols, 1), owned) ||
+        sp_dmalloc(&q, cols, owned) || sp_dmalloc(&partials, kMaxParts, owned) ||
+        sp_dmalloc(&st, 1, owned))
       return -1;
-    std::vector<void*> tmp;
-    struct TmpFree {
-      std::vector<void*>& v;
-      hipStream_t s;
-      ~TmpFree() {
-        (void)hipStreamSynchronize(s);
-        for (void* q_ : v) (void)hipFree(q_);
-      }
-    } tmp_free{tmp, s};
-    if (dmalloc(&rp32, rows + 1, tmp) || dmalloc(&rp0, rows + 1, tmp) ||
-        dmalloc(&ci0, nnz, tmp) || dmalloc(&v0, nnz, tmp))
-      return -1;
-    MR_H2D(rp32, hrp, (rows + 1) * 4, s);
-    if (nnz) {
-      MR_H2D(ci0, hci, nnz * 4, s);
-      MR_H2D(v0, hv, nnz * 8, s);
-    }
-    if (launch_i32_to_i64(s, rows + 1, rp32, rp0)) return -1;
-    // rows ordered by first column (a row permutation: same solution, same
-    // row sums), so A^T's rows read t in runs and A's rows gather r, p from
-    // neighbouring columns (csr_build.hip sort_rows_by_first_col)
-    if (sort_rows_by_first_col(s, rows, cols, rp0, ci0, v0, perm, rp, ci, v)) return -1;
-    for (void* q_ : {(void*)rp32, (void*)rp0, (void*)ci0, (void*)v0}) {
-      (void)hipStreamSynchronize(s);
-      (void)hipFree(q_);
-    }
-    tmp.clear();
-    if (dmalloc(&rowof, nnz, tmp)) return -1;
-    // explicit transpose (sparse_matrix_transpose, matrix.cpp:617-692): a
-    // stable sort of the non-zeros by column keeps each column's rows in order
-    if (launch_rows_of(s, rows, rp, rowof)) return -1;
-    if (build_csr<double, double>(s, nnz, cols, ci, 0, rowof, v, tp, ti, tv)) return -1;
-    // row blocks of A and of A^T (offsets read back once)
-    std::vector<int64_t> offa(rows + 1), offt(cols + 1);
-    MR_D2H(offa.data(), rp, (rows + 1) * 8, s);
-    MR_D2H(offt.data(), tp, (cols + 1) * 8, s);
-    // uploaded as (first row, its first non-zero) pairs: the kernels read a
-    // block's bounds with no dependent load through the row offsets
-    auto pairs = [](const std::vector<int64_t>& bl, const std::vector<int64_t>& off) {
-      std::vector<int64_t> pr(2 * bl.size());
-      for (size_t i = 0; i < bl.size(); ++i) {
-        pr[2 * i] = bl[i];
-        pr[2 * i + 1] = off[bl[i]];
-      }
-      return pr;
-    };
-    const std::vector<int64_t> ba = pairs(row_blocks(offa), offa),
-                               bt = pairs(row_blocks(offt), offt);
-    n_blk_a = (int64_t)ba.size() / 2 - 1;
-    n_blk_t = (int64_t)bt.size() / 2 - 1;
-    if (dmalloc(&blk_a, (int64_t)ba.size(), owned) || dmalloc(&blk_t, (int64_t)bt.size(), owned))
-      return -1;
-    MR_H2D(blk_a, ba.data(), ba.size() * 8, s);
-    MR_H2D(blk_t, bt.data(), bt.size() * 8, s);
-    MR_HIP(hipStreamSynchronize(s));
     stats.rows = rows;
     stats.cols = cols;
     stats.nnz = nnz;

@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "mr_internal.h"
+#include "lsqr_device.h"
 
 
 namespace mr {
@@ -4644,11 +4645,25 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
     const double* __restrict__ v, const double* __restrict__ xa, const double* __restrict__ xb,
     uint32_t xbytes,
     double* __restrict__ out, double* __restrict__ pv, const double* __restrict__ rv,
-    int update_p, double* __restrict__ partials, CgState* fst) {
+    int update_p, double* __restrict__ partials, CgState* fst, LsqrState* ls, int lmode) {
 #pragma clang fp contract(off)
   if (st && ald(&st->done)) return;
   const double beta = (st && (GATHER == SPG_P || update_p)) ? ald(&st->beta) : 0.0;
   static_assert(OUT != SPO_CG || GATHER == SPG_X, "the CG output pass gathers t");
+  static_assert((OUT == SPO_LSQR) == (GATHER == SPG_S), "the LSQR passes gather a scaled vector");
+  // LSQR (lsqr_device.h): out_row = sum_c a_rc (lg x_c) - lc (ls_ out_row), or
+  // its negative (LSQR_NEG: the setup's u = b - A x0); KA reads (alfa, us, vs),
+  // KT (beta, vs, us)
+  double lg = 0.0, lc = 0.0, ls_ = 0.0;
+  if constexpr (OUT == SPO_LSQR) {
+    if (ald(&ls->done)) return;
+    const bool kt = (lmode & LSQR_KT) != 0;
+    const double us = ald(&ls->us), vs = ald(&ls->vs);
+    lg = kt ? us : vs;
+    ls_ = kt ? vs : us;
+    lc = kt ? ald(&ls->beta) : ald(&ls->alfa);
+    if (kt && ald(&ls->skip_t)) n_blk = 0;   // beta == 0: only the scalar rule runs
+  }
   __shared__ double prod[SP_TILE];
   __shared__ double sh[SP_THREADS / 64];
   const int t = threadIdx.x;
@@ -4665,6 +4680,11 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
       else
         w = reinterpret_cast<const double2*>(xa)[c];
       return -1.0 * w.x + beta * w.y;
+    } else if constexpr (GATHER == SPG_S) {
+      if constexpr (BUF)
+        return lg * __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(ra, (int)((uint32_t)c * 8u), 0, 0));
+      else
+        return lg * xa[c];
     } else {
       const uint32_t i = GATHER == SPG_P0 ? 2u * (uint32_t)c + 1u : (uint32_t)c;
       if constexpr (BUF)
@@ -4674,7 +4694,18 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
     }
   };
   double probe_sink = 0.0;
+  // the LSQR output pass on a row's sum and the row's stored value
+  auto emit_lsqr = [&](int64_t row, double s, double old) {
+    const double sub = lc * (ls_ * old);
+    const double nv = (lmode & LSQR_NEG) ? sub - s : s - sub;
+    out[row] = nv;
+    d += nv * nv;
+  };
   auto emit = [&](int64_t row, double s) {
+    if constexpr (OUT == SPO_LSQR) {
+      emit_lsqr(row, s, out[row]);
+      return;
+    }
     if (MR_SP_PROBE & 4) probe_sink += s;
     else if (MR_SP_OUT == 1) __builtin_nontemporal_store(s, out + row);
     else if (MR_SP_OUT == 2) asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(out + row), "v"(s) : "memory");
@@ -4711,6 +4742,7 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
   constexpr int PER = SP_TILE / SP_THREADS;
   __shared__ int32_t srp[kSpMaxRows + 1];   // the block's row offsets - n0
   __shared__ double2 spv[OUT == SPO_CG && MR_SP_PRELOAD && MR_SP_ORDER ? kSpMaxRows : 1];   // their (r, p) pairs
+  __shared__ double sov[OUT == SPO_LSQR ? kSpMaxRows : 1];   // LSQR: the rows' stored values
   struct Stage {
     int32_t cc[PER];
     double vv[PER];
@@ -4791,6 +4823,7 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
     const bool cur_short = n1 - n0 <= SP_TILE;
     double gx[PER];
     double2 rpair;   // OUT == SPO_CG: row r0 + t's (r, p) pair, loaded with the gathers
+    double oldv = 0.0;   // OUT == SPO_LSQR: row r0 + t's stored value, loaded with the gathers
     if (MR_SP_ORDER && cur_short) {
       // this block's gathers first, then the next block's stream: waiting for
       // the gathers (in-order vmcnt) then leaves the stream in flight
@@ -4799,6 +4832,10 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
       if constexpr (OUT == SPO_CG && MR_SP_PRELOAD) {
         const int64_t nr = r1 - r0;
         rpair = reinterpret_cast<const double2*>(pv)[r0 + (t < nr ? t : nr - 1)];
+      }
+      if constexpr (OUT == SPO_LSQR) {
+        const int64_t nr = r1 - r0;   // >= 1: a block holds a row at least
+        oldv = out[r0 + (t < nr ? t : nr - 1)];
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -4842,6 +4879,11 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
       if constexpr (OUT == SPO_CG && MR_SP_PRELOAD && MR_SP_ORDER) {
         if (t < R) spv[t] = rpair;
       }
+      if constexpr (OUT == SPO_LSQR) {
+        if (MR_SP_ORDER) {
+          if (t < R) sov[t] = oldv;
+        }
+      }
       __syncthreads();
       int G = 1;
       while (G < 64 && 2 * G * R <= SP_THREADS) G *= 2;
@@ -4865,6 +4907,7 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
       for (int o = G / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
       if (lr < R && g == 0) {
         if constexpr (OUT == SPO_CG && MR_SP_PRELOAD && MR_SP_ORDER) emit_cg(r0 + lr, sum, spv[lr]);
+        else if constexpr (OUT == SPO_LSQR && MR_SP_ORDER) emit_lsqr(r0 + lr, sum, sov[lr]);
         else emit(r0 + lr, sum);
       }
       __syncthreads();   // prod / srp are reused by the next block
@@ -4891,6 +4934,14 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
     } else if (t == 0) {
       partials[blockIdx.x] = tot;
     }
+  }
+  if constexpr (OUT == SPO_LSQR) {
+    const double tot = block_sum_f64<SP_THREADS>(d, sh);
+    __syncthreads();   // sh is reused by the last workgroup's sum
+    lsqr_last_block(ls, partials, tot, sh, [&](double total) {
+      if (lmode & LSQR_KT) lsqr_after_t(ls, total);
+      else lsqr_after_a(ls, total);
+    });
   }
 }
 
@@ -4935,10 +4986,10 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
 #define MR_SP(GA, OU)                                                                      \
   if (buf)                                                                                  \
     MR_LAUNCH((csr_spmv_kernel<GA, OU, true>), grid, dim3(SP_THREADS), 0, s, st, n_blk, blk, \
-              rp, ci, v, xa, xb, xbytes, out, pv, rv, update_p, partials, fst);            \
+              rp, ci, v, xa, xb, xbytes, out, pv, rv, update_p, partials, fst, nullptr, 0); \
   else                                                                                      \
     MR_LAUNCH((csr_spmv_kernel<GA, OU, false>), grid, dim3(SP_THREADS), 0, s, st, n_blk,    \
-              blk, rp, ci, v, xa, xb, xbytes, out, pv, rv, update_p, partials, fst)
+              blk, rp, ci, v, xa, xb, xbytes, out, pv, rv, update_p, partials, fst, nullptr, 0)
   if (out_mode == SPO_CG) {
     MR_SP(SPG_X, SPO_CG);
   } else {
@@ -4947,6 +4998,41 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
     else MR_SP(SPG_X, SPO_STORE);
   }
 #undef MR_SP
+  MR_HIP(hipGetLastError());
+  return 0;
+}
+
+// The LSQR passes KA / KT (lsqr_device.h) on the same grid rule as
+// launch_csr_spmv: out = A (scaled xa) - c (scaled out), sum out^2 into
+// partials[n_part], the last workgroup applies the scalar rule of lmode.
+int launch_csr_spmv_lsqr(hipStream_t s, LsqrState* ls, int lmode, int64_t n_blk,
+                         const int64_t* blk, const int64_t* rp, const int32_t* ci,
+                         const double* v, const double* xa, int64_t nx, double* out,
+                         double* partials, int n_part, bool ptr_loads) {
+  if (n_blk <= 0) {
+    set_error("LSQR pass without row blocks");
+    return -1;
+  }
+  int dev = 0, cus = 0;
+  MR_HIP(hipGetDevice(&dev));
+  MR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const bool buf = !ptr_loads && nx >= 0 && nx * 8 < (int64_t)0xFFFFFFF0;
+  const void* fn = buf ? (const void*)csr_spmv_kernel<SPG_S, SPO_LSQR, true>
+                       : (const void*)csr_spmv_kernel<SPG_S, SPO_LSQR, false>;
+  int bpc = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, SP_THREADS, 0) != hipSuccess) bpc = 0;
+  int64_t parts = n_part;
+  if (bpc > 0 && cus > 0) parts = std::min<int64_t>(parts, (int64_t)bpc * cus);
+  const dim3 grid((unsigned)std::min<int64_t>(n_blk, parts));
+  const uint32_t xbytes = buf ? (uint32_t)(nx * 8) : 0u;
+  if (buf)
+    MR_LAUNCH((csr_spmv_kernel<SPG_S, SPO_LSQR, true>), grid, dim3(SP_THREADS), 0, s, nullptr,
+              n_blk, blk, rp, ci, v, xa, nullptr, xbytes, out, nullptr, nullptr, 0, partials,
+              nullptr, ls, lmode);
+  else
+    MR_LAUNCH((csr_spmv_kernel<SPG_S, SPO_LSQR, false>), grid, dim3(SP_THREADS), 0, s, nullptr,
+              n_blk, blk, rp, ci, v, xa, nullptr, xbytes, out, nullptr, nullptr, 0, partials,
+              nullptr, ls, lmode);
   MR_HIP(hipGetLastError());
   return 0;
 }

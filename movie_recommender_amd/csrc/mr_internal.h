@@ -430,8 +430,9 @@ int launch_predict(hipStream_t s, int64_t n, int k, int ldk, const int* uid,
 // xa = rp.  out SPO_STORE: out[row] = sum; SPO_CG: out[row] = q_row, p_row
 // updated in pv = rp (update_p) and p.q summed, the last workgroup computes
 // alpha (fst, partials[n_part]).  nx: doubles in the gathered array.
-enum SpGather { SPG_X = 0, SPG_P = 1, SPG_P0 = 2 };
-enum SpOut { SPO_STORE = 0, SPO_CG = 1 };
+// SPG_S / SPO_LSQR: the LSQR passes (launch_csr_spmv_lsqr, lsqr_device.h).
+enum SpGather { SPG_X = 0, SPG_P = 1, SPG_P0 = 2, SPG_S = 3 };
+enum SpOut { SPO_STORE = 0, SPO_CG = 1, SPO_LSQR = 2 };
 constexpr int kSpTile = 2048;
 constexpr int kSpPad = 16;   // entries past nnz every SpMV id / value array holds
 constexpr int kSpMaxRows = 256;
@@ -442,6 +443,11 @@ int launch_csr_spmv(hipStream_t s, int gather, int out_mode, const CgState* st, 
                     CgState* fst, bool ptr_loads = false);
 // nx: length of the gathered vector(s) xa / xb; ptr_loads: the pointer-load
 // twin even where nx would allow buffer loads (mr_cg_set_gather_path)
+struct LsqrState;
+int launch_csr_spmv_lsqr(hipStream_t s, LsqrState* ls, int lmode, int64_t n_blk,
+                         const int64_t* blk, const int64_t* rp, const int32_t* ci,
+                         const double* v, const double* xa, int64_t nx, double* out,
+                         double* partials, int n_part, bool ptr_loads);
 int launch_cgls_update(hipStream_t s, const CgState* st, int mode, int64_t n, double* x,
                        double* rp, const double* q, const double* b2,
                        double* partials, int n_part, CgState* fst, CgMirror* mirror, int seq);
