@@ -73,6 +73,20 @@ int mr_lsqr_set_values_from_table(mr_lsqr* ctx, const double* table, long long t
 int mr_lsqr_solve(mr_lsqr* ctx, const double* b, const double* x0_or_null, double damp,
                   double atol, double btol, double conlim, int iter_lim, double* x_out,
                   mr_lsqr_result* out);
+/* scipy.sparse.linalg.lsmr(A, b, damp, atol, btol, conlim, maxiter, x0=x0) on
+ * the same context (values, value map, gather path, timing and stats as
+ * mr_lsqr_solve; solves of both kinds may alternate): the solver restates
+ * scipy/sparse/linalg/_isolve/lsmr.py (1.15) operation for operation, show
+ * is not offered.  KA and KT are LSQR's kernels; KX updates h, hbar and x and
+ * sums x^2.  Timings go into the four classes above.  *out as SciPy's istop,
+ * itn, normr, normar, norma, conda, normx.  0, or < 0 on error. */
+typedef struct mr_lsmr_result {
+  int istop, itn;
+  double normr, normar, norma, conda, normx;
+} mr_lsmr_result;
+int mr_lsqr_solve_lsmr(mr_lsqr* ctx, const double* b, const double* x0_or_null, double damp,
+                       double atol, double btol, double conlim, int maxiter, double* x_out,
+                       mr_lsmr_result* out);
 /* *out = sum_i |b_i - (A x)_i|, one pass over A. */
 int mr_lsqr_residual_l1(mr_lsqr* ctx, const double* b, const double* x, double* out);
 

@@ -12,6 +12,7 @@ Modules
   content     tag least-squares content model (``include/mr_content.h``)
   tagcount    tag-count content model, median predictor (``include/mr_tagcount.h``)
   lsqr        general sparse LSQR and the SciPy-style ALS on it (``include/mr_lsqr.h``)
+  lsmr        SciPy's LSMR on the same resident matrix, and the ALS with it
   distributed one process per GPU, users/items sharded, factor all-gather
   synth       seeded MovieLens-shaped ratings (benchmarks, statistical tests)
   build       compiles ``lib/cpp_ls_lib.so`` with hipcc for gfx950

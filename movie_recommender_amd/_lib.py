@@ -123,6 +123,13 @@ class MrLsqrResult(ctypes.Structure):
                 ("arnorm", ctypes.c_double), ("xnorm", ctypes.c_double)]
 
 
+class MrLsmrResult(ctypes.Structure):
+    _fields_ = [("istop", ctypes.c_int), ("itn", ctypes.c_int),
+                ("normr", ctypes.c_double), ("normar", ctypes.c_double),
+                ("norma", ctypes.c_double), ("conda", ctypes.c_double),
+                ("normx", ctypes.c_double)]
+
+
 class MrComm(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p),
                 ("rank", ctypes.c_int),
@@ -228,6 +235,9 @@ SIGNATURES = {
     "mr_lsqr_solve": (ctypes.c_int, [VP, DP, DP, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_int, DP,
                                      ctypes.POINTER(MrLsqrResult)]),
+    "mr_lsqr_solve_lsmr": (ctypes.c_int, [VP, DP, DP, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, DP,
+                                          ctypes.POINTER(MrLsmrResult)]),
     "mr_lsqr_residual_l1": (ctypes.c_int, [VP, DP, DP, DP]),
     "mr_lsqr_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
     "mr_lsqr_set_gather_path": (ctypes.c_int, [VP, ctypes.c_int]),

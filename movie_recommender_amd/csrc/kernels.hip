@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "mr_internal.h"
+#include "lsmr_device.h"
 #include "lsqr_device.h"
 
 
@@ -4939,8 +4940,15 @@ __global__ __launch_bounds__(SP_THREADS) void csr_spmv_kernel(
     const double tot = block_sum_f64<SP_THREADS>(d, sh);
     __syncthreads();   // sh is reused by the last workgroup's sum
     lsqr_last_block(ls, partials, tot, sh, [&](double total) {
-      if (lmode & LSQR_KT) lsqr_after_t(ls, total);
-      else lsqr_after_a(ls, total);
+      if (lmode & LSQR_LSMR) {   // ls is the head of an LsmrState (lsmr_device.h)
+        LsmrState* lm = reinterpret_cast<LsmrState*>(ls);
+        if (lmode & LSQR_KT) lsmr_after_t(lm, total);
+        else lsmr_after_a(lm, total);
+      } else if (lmode & LSQR_KT) {
+        lsqr_after_t(ls, total);
+      } else {
+        lsqr_after_a(ls, total);
+      }
     });
   }
 }

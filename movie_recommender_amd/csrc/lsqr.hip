@@ -12,6 +12,10 @@
 // scalars live in the device LsqrState, every KX publishes (itn, istop, done)
 // into a host-mapped seqlock ring, and the host keeps a few iterations
 // enqueued ahead (the protocol of CgLs::solve).
+//
+// LSMR (mr_lsqr_solve_lsmr; lsmr_device.h) runs on the same context: the
+// same KA / KT with the LSQR_LSMR bit, its own state, KX = lsmr_x_kernel on
+// (h = w, hbar), the same host loop.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,6 +23,7 @@
 
 #include "../../include/mr_lsqr.h"
 #include "engine.h"
+#include "lsmr_device.h"
 #include "lsqr_device.h"
 #include "sp_structure.h"
 
@@ -56,6 +61,40 @@ __global__ __launch_bounds__(kLsqrThreads) void lsqr_x_kernel(
   const double tot = lsqr_block_sum(acc, sh);
   lsqr_last_block(st, partials, tot, sh,
                   [&](double total) { lsqr_after_x(st, total, mirror, seq); });
+}
+
+// LSMR's KX: hbar = hbar ch + h, x = x + cx hbar, h = h chh + v with v = vs vh
+// (lsmr.py:365-369), sum x^2 on the new x (:413); in the setup h = v, hbar = 0
+// (:268-269).  The last workgroup applies lsmr_after_x.
+__global__ __launch_bounds__(kLsqrThreads) void lsmr_x_kernel(
+    LsmrState* st, int64_t n, double* __restrict__ x, double* __restrict__ h,
+    double* __restrict__ hbar, const double* __restrict__ vh, double* __restrict__ partials,
+    CgMirror* mirror, int seq) {
+#pragma clang fp contract(off)
+  if (st->q.done) return;
+  __shared__ double sh[4];
+  const bool setup = st->q.setup != 0;
+  const double vs = st->q.vs, ch = st->ch, cx = st->cx, chh = st->chh;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double v = vs * vh[i];
+    if (setup) {
+      h[i] = v;
+      hbar[i] = 0.0;
+    } else {
+      const double hi = h[i];
+      const double hb = hbar[i] * ch + hi;
+      hbar[i] = hb;
+      const double xi = x[i] + cx * hb;
+      x[i] = xi;
+      h[i] = hi * chh + v;
+      acc += xi * xi;
+    }
+  }
+  const double tot = lsqr_block_sum(acc, sh);
+  lsqr_last_block(&st->q, partials, tot, sh,
+                  [&](double total) { lsmr_after_x(st, total, mirror, seq); });
 }
 
 // bnorm = sqrt(sum b_i^2) (lsqr.py:374) when x0 is given.
@@ -132,6 +171,11 @@ struct Lsqr : LaunchTimer {
          *partials = nullptr, *scal = nullptr;
   LsqrState* st = nullptr;
   LsqrState* h_st = nullptr;   // pinned: the initial state up, the final state down
+  // LSMR: allocated by the context's first LSMR solve
+  double* hbar = nullptr;
+  LsmrState *lm = nullptr, *h_lm = nullptr;
+  LsqrState* cur = nullptr;    // the running solve's state (st, or lm's head)
+  int cur_mode = 0;            // 0, or LSQR_LSMR
   CgMirror *h_mirror = nullptr, *d_mirror = nullptr;
   int seq = 0;
   bool ptr_loads = false;
@@ -144,6 +188,7 @@ struct Lsqr : LaunchTimer {
     for (void* q_ : owned) (void)hipFree(q_);
     if (tab) (void)hipFree(tab);
     if (h_st) (void)hipHostFree(h_st);
+    if (h_lm) (void)hipHostFree(h_lm);
     if (h_mirror) (void)hipHostFree(h_mirror);
     destroy_events();
     (void)hipStreamDestroy(s);
@@ -261,17 +306,22 @@ struct Lsqr : LaunchTimer {
 
   int pass(int lmode) {
     const bool kt = (lmode & LSQR_KT) != 0;
+    lmode |= cur_mode;
     if (kt)
-      return launch_csr_spmv_lsqr(s, st, lmode, sp.n_blk_t, sp.blk_t, sp.tp, sp.ti, sp.tv, uh, rows,
+      return launch_csr_spmv_lsqr(s, cur, lmode, sp.n_blk_t, sp.blk_t, sp.tp, sp.ti, sp.tv, uh, rows,
                                   vh, partials, kMaxParts, ptr_loads);
-    return launch_csr_spmv_lsqr(s, st, lmode, sp.n_blk_a, sp.blk_a, sp.rp, sp.ci, sp.v,
+    return launch_csr_spmv_lsqr(s, cur, lmode, sp.n_blk_a, sp.blk_a, sp.rp, sp.ci, sp.v,
                                 (lmode & LSQR_NEG) ? x : vh, cols, uh, partials, kMaxParts,
                                 ptr_loads);
   }
 
   int kx(int sq) {
-    MR_LAUNCH(lsqr_x_kernel, dim3(grid_of(cols, kUpdParts)), dim3(kLsqrThreads), 0, s, st, cols, x,
-              w, vh, partials, d_mirror, sq);
+    if (cur_mode & LSQR_LSMR)
+      MR_LAUNCH(lsmr_x_kernel, dim3(grid_of(cols, kUpdParts)), dim3(kLsqrThreads), 0, s, lm, cols,
+                x, w, hbar, vh, partials, d_mirror, sq);
+    else
+      MR_LAUNCH(lsqr_x_kernel, dim3(grid_of(cols, kUpdParts)), dim3(kLsqrThreads), 0, s, st, cols,
+                x, w, vh, partials, d_mirror, sq);
     MR_HIP(hipGetLastError());
     return 0;
   }
@@ -283,11 +333,52 @@ struct Lsqr : LaunchTimer {
     return 0;
   }
 
+  // rows == 0 or cols == 0 (lsmr.py:237-303 by hand): alpha = 0, so normar == 0
+  // returns x0 at once with normA = 0, condA = 1
+  int solve_empty_lsmr(const double* hb, const double* hx0, double* hx, mr_lsmr_result* out) {
+    double ss = 0.0;
+    for (int64_t i = 0; i < rows; ++i) ss += hb[i] * hb[i];
+    for (int64_t j = 0; j < cols; ++j) hx[j] = hx0 ? hx0[j] : 0.0;
+    *out = mr_lsmr_result{0, 0, std::sqrt(ss), 0.0, 0.0, 1.0, 0.0};
+    stats.last_iterations = 0;
+    return 0;
+  }
+
   int solve(const double* hb, const double* hx0, double damp, double atol, double btol,
             double conlim, int iter_lim, double* hx, mr_lsqr_result* out) {
     MR_CHECK(out, "null result");
     MR_CHECK((hb || rows == 0) && (hx || cols == 0), "null b or x");
     if (rows == 0 || cols == 0) return solve_empty(hb, hx0, hx, out);
+    if (run(0, hb, hx0, damp, atol, btol, conlim, iter_lim, hx)) return -1;
+    *out = mr_lsqr_result{h_st->istop, h_st->itn,   h_st->r1norm, h_st->r2norm,
+                          h_st->anorm, h_st->acond, h_st->arnorm, h_st->xnorm};
+    return 0;
+  }
+
+  int solve_lsmr(const double* hb, const double* hx0, double damp, double atol, double btol,
+                 double conlim, int maxiter, double* hx, mr_lsmr_result* out) {
+    MR_CHECK(out, "null result");
+    MR_CHECK((hb || rows == 0) && (hx || cols == 0), "null b or x");
+    if (rows == 0 || cols == 0) return solve_empty_lsmr(hb, hx0, hx, out);
+    MR_HIP(hipSetDevice(device));
+    if (!h_lm) MR_HIP(hipHostMalloc((void**)&h_lm, sizeof(LsmrState), hipHostMallocDefault));
+    if ((!hbar && sp_dmalloc(&hbar, cols, owned)) || (!lm && sp_dmalloc(&lm, 1, owned))) return -1;
+    if (run(LSQR_LSMR, hb, hx0, damp, atol, btol, conlim, maxiter, hx)) return -1;
+    if (h_lm->zero_x) std::fill(hx, hx + cols, 0.0);   // x[()] = 0 (lsmr.py:305-307)
+    *out = mr_lsmr_result{h_lm->q.istop, h_lm->q.itn, h_lm->normr, h_lm->normar,
+                          h_lm->normA,   h_lm->condA, h_lm->normx};
+    return 0;
+  }
+
+  // One solve of either kind (mode: 0, or LSQR_LSMR); the final state is left
+  // in h_st / h_lm, x in hx.
+  int run(int mode, const double* hb, const double* hx0, double damp, double atol, double btol,
+          double conlim, int iter_lim, double* hx) {
+    const bool lsmr = (mode & LSQR_LSMR) != 0;
+    cur_mode = mode;
+    cur = lsmr ? &lm->q : st;
+    LsqrState* h_cur = lsmr ? &h_lm->q : h_st;
+    const size_t st_bytes = lsmr ? sizeof(LsmrState) : sizeof(LsqrState);
     MR_HIP(hipSetDevice(device));
     MR_H2D(b_in, hb, rows * 8, s);
     if (launch_gather_f64(s, rows, sp.perm, b_in, uh)) return -1;   // u = b in the rows' order
@@ -299,23 +390,23 @@ struct Lsqr : LaunchTimer {
       if (ev(&e0) || ev(&e1)) return -1;
       MR_HIP(hipEventRecord(e0, s));
     }
-    memset(h_st, 0, sizeof(LsqrState));
-    h_st->alfa = 1.0;   // the setup's KA: u = 1 * (1 * b) - A x0
-    h_st->us = 1.0;
-    h_st->vs = 1.0;
-    h_st->cs2 = -1.0;
-    h_st->damp = damp;
-    h_st->dampsq = damp * damp;
-    h_st->atol = atol;
-    h_st->btol = btol;
-    h_st->ctol = conlim > 0.0 ? 1.0 / conlim : 0.0;
-    h_st->iter_lim = iter_lim;
-    h_st->setup = 1;
-    h_st->bnorm_is_beta = hx0 ? 0 : 1;
-    MR_HIP(hipMemcpyAsync(st, h_st, sizeof(LsqrState), hipMemcpyHostToDevice, s));
+    memset((void*)h_cur, 0, st_bytes);
+    h_cur->alfa = 1.0;   // the setup's KA: u = 1 * (1 * b) - A x0
+    h_cur->us = 1.0;
+    h_cur->vs = 1.0;
+    h_cur->cs2 = -1.0;
+    h_cur->damp = damp;
+    h_cur->dampsq = damp * damp;
+    h_cur->atol = atol;
+    h_cur->btol = btol;
+    h_cur->ctol = conlim > 0.0 ? 1.0 / conlim : 0.0;
+    h_cur->iter_lim = iter_lim;
+    h_cur->setup = 1;
+    h_cur->bnorm_is_beta = hx0 ? 0 : 1;
+    MR_HIP(hipMemcpyAsync(cur, h_cur, st_bytes, hipMemcpyHostToDevice, s));
     if (tic(MR_LSQR_K_SETUP, -1)) return -1;
     if (hx0) {
-      MR_LAUNCH(lsqr_bnorm_kernel, dim3(grid_of(rows, kUpdParts)), dim3(kLsqrThreads), 0, s, st,
+      MR_LAUNCH(lsqr_bnorm_kernel, dim3(grid_of(rows, kUpdParts)), dim3(kLsqrThreads), 0, s, cur,
                 rows, b_in, partials);
       MR_HIP(hipGetLastError());
     }
@@ -345,7 +436,7 @@ struct Lsqr : LaunchTimer {
       ++known;
     }
     if (timing) MR_HIP(hipEventRecord(e1, s));
-    MR_HIP(hipMemcpyAsync(h_st, st, sizeof(LsqrState), hipMemcpyDeviceToHost, s));
+    MR_HIP(hipMemcpyAsync(h_cur, cur, st_bytes, hipMemcpyDeviceToHost, s));
     MR_D2H(hx, x, cols * 8, s);
     MR_HIP(hipStreamSynchronize(s));
     if (timing) {
@@ -355,7 +446,7 @@ struct Lsqr : LaunchTimer {
       pool.push_back(e0);
       pool.push_back(e1);
       for (auto& tm : pend) {
-        if (tm.it < h_st->itn) {   // setup (-1) and the iterations that did work
+        if (tm.it < h_cur->itn) {   // setup (-1) and the iterations that did work
           MR_HIP(hipEventElapsedTime(&ms_, tm.a, tm.b));
           stats.kernel_ms[tm.cls] += ms_;
           stats.kernel_launches[tm.cls] += 1;
@@ -365,10 +456,8 @@ struct Lsqr : LaunchTimer {
       }
       pend.clear();
     }
-    *out = mr_lsqr_result{h_st->istop, h_st->itn,   h_st->r1norm, h_st->r2norm,
-                          h_st->anorm, h_st->acond, h_st->arnorm, h_st->xnorm};
-    stats.last_iterations = h_st->itn;
-    stats.iterations_total += h_st->itn;
+    stats.last_iterations = h_cur->itn;
+    stats.iterations_total += h_cur->itn;
     return 0;
   }
 
@@ -464,6 +553,15 @@ int mr_lsqr_solve(mr_lsqr* ctx, const double* b, const double* x0_or_null, doubl
   MR_CHECK(ctx, "null context");
   return lsqr_guarded([&]() {
     return ctx->c.solve(b, x0_or_null, damp, atol, btol, conlim, iter_lim, x_out, out);
+  });
+}
+
+int mr_lsqr_solve_lsmr(mr_lsqr* ctx, const double* b, const double* x0_or_null, double damp,
+                       double atol, double btol, double conlim, int maxiter, double* x_out,
+                       mr_lsmr_result* out) {
+  MR_CHECK(ctx, "null context");
+  return lsqr_guarded([&]() {
+    return ctx->c.solve_lsmr(b, x0_or_null, damp, atol, btol, conlim, maxiter, x_out, out);
   });
 }
 

@@ -39,7 +39,8 @@ struct LsqrState {
   uint32_t arrive;       // workgroups finished (the last one applies the rule)
 };
 
-enum LsqrMode { LSQR_KT = 1, LSQR_NEG = 2 };   // csr_spmv_kernel's lmode bits
+// csr_spmv_kernel's lmode bits (LSQR_LSMR: the rules of lsmr_device.h)
+enum LsqrMode { LSQR_KT = 1, LSQR_NEG = 2, LSQR_LSMR = 4 };
 
 __device__ __forceinline__ double lsqr_sign(double a) {
   return a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : a);   // np.sign: 0 -> 0, nan -> nan

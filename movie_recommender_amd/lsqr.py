@@ -4,7 +4,8 @@ SciPy ALS on top of it.
 ``lsqr`` takes ``scipy.sparse.linalg.lsqr``'s arguments and returns its
 10-tuple; the solver restates SciPy's (1.15) operation for operation on the
 device.  ``LsqrContext`` keeps a matrix's structure on the device for any
-number of solves and value updates.  ``als_lsqr`` is the reference's
+number of solves and value updates; ``LsqrContext.solve_lsmr`` is SciPy's
+LSMR on the same resident matrix (the ``lsmr`` module wraps it).  ``als_lsqr`` is the reference's
 ``fit_to_data`` (``python/100k_data/ratings_als.py:502-529``): one global
 LSQR on the design matrix per half-step, the two design matrices' structure
 built once and their values gathered on the device from the factor tables.
@@ -126,6 +127,32 @@ class LsqrContext:
                    "r2norm": res.r2norm, "anorm": res.anorm, "acond": res.acond,
                    "arnorm": res.arnorm, "xnorm": res.xnorm}
 
+    def solve_lsmr(self, b, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=None, x0=None):
+        """LSMR on the resident matrix: (x, result) with result = dict(istop,
+        itn, normr, normar, norma, conda, normx), as
+        ``scipy.sparse.linalg.lsmr`` defines them; ``maxiter=None`` means
+        min(rows, columns), SciPy's rule for LSMR."""
+        b = _vec(b, self.rows, "b")
+        x0p = None
+        if x0 is not None:
+            x0 = _vec(x0, self.cols, "x0")
+            x0p = x0.ctypes.data_as(_lib.DP)
+        if maxiter is None:
+            maxiter = min(self.rows, self.cols)
+        maxiter = int(maxiter)
+        if maxiter >= 2 ** 31:
+            raise ValueError("maxiter exceeds int32")
+        x = np.zeros(self.cols, np.float64)
+        res = _lib.MrLsmrResult()
+        _lib.check(self._L.mr_lsqr_solve_lsmr(self._handle(), b.ctypes.data_as(_lib.DP), x0p,
+                                              float(damp), float(atol), float(btol),
+                                              float(conlim), maxiter, x.ctypes.data_as(_lib.DP),
+                                              ctypes.byref(res)),
+                   "mr_lsqr_solve_lsmr")
+        return x, {"istop": res.istop, "itn": res.itn, "normr": res.normr,
+                   "normar": res.normar, "norma": res.norma, "conda": res.conda,
+                   "normx": res.normx}
+
     def set_values(self, values):
         """New values for the same structure, in the order given at creation."""
         v = _vec(values, self.nnz, "values")
@@ -211,6 +238,14 @@ def als_lsqr(user_ids, item_ids, ratings, k, num_users, num_items, movies0=None,
     ``callback(info)`` is called after every iteration with the iteration
     number, copies of both tables, the error and each half-step's LSQR result.
     """
+    return _als(lambda ctx, rhs: ctx.solve(rhs, iter_lim=iter_lim), user_ids, item_ids, ratings,
+                k, num_users, num_items, movies0, seed, max_iterations, device, callback)
+
+
+def _als(solve, user_ids, item_ids, ratings, k, num_users, num_items, movies0, seed,
+         max_iterations, device, callback):
+    """The loop of ``als_lsqr`` / ``lsmr.als_lsmr``: ``solve(ctx, rhs)`` is one
+    half-step's global solve on an ``LsqrContext``, returning (x, result)."""
     uid = np.ascontiguousarray(user_ids, np.int64).ravel()
     iid = np.ascontiguousarray(item_ids, np.int64).ravel()
     r = np.ascontiguousarray(ratings, np.float64).ravel()
@@ -246,10 +281,10 @@ def als_lsqr(user_ids, item_ids, ratings, k, num_users, num_items, movies0=None,
         old_error = None
         for it in range(int(max_iterations)):
             cu.set_values_from_table(movies)
-            users, ru = cu.solve(r, iter_lim=iter_lim)
+            users, ru = solve(cu, r)
             cm.set_values_from_table(users)
             rhs = r - users[k::k + 1][uid]
-            movies, rm = cm.solve(rhs, iter_lim=iter_lim)
+            movies, rm = solve(cm, rhs)
             error = cm.residual_l1(rhs, movies) / n
             errors.append(error)
             iterations = it + 1
