@@ -953,10 +953,8 @@ bool Engine::onepass_for(const Side& S) const {
 }
 
 // The user-side rhs / row sums on the matrix cores (the W block) from NB =
-// MR_RHSM_MIN_NB up (A/B knob; below it they stay on the VALU)
-#ifndef MR_RHSM_MIN_NB
-#define MR_RHSM_MIN_NB 5
-#endif
+// MR_RHSM_MIN_NB up (below it they stay on the VALU)
+constexpr int MR_RHSM_MIN_NB = 5;
 
 // start: the Gram waves also start the CG solve (r0, p0, q0 = G p0 and the
 // block pairs of r.r / p.Gp); Engine::cg(started = true) finishes the start.

@@ -294,15 +294,10 @@ int launch_gram(hipStream_t s, bool user_side, int k, const WorkItem* work,
                 const float* F, const float* bias, int zrow, GramDst direct,
                 GramDst slab, const CgStart* start = nullptr, bool rhs_mfma = false);
 // Gram blocks of a launch over n_work work items: four one-wave items per
-// block, or (k = 113 ... 128, MR_GRAM_PAIR) one item per pair-of-waves block
-#ifndef MR_GRAM_PAIR
-#define MR_GRAM_PAIR 1
-#endif
-inline bool gram_pair_of(int k) { return MR_GRAM_PAIR && k > 112 && k <= 128; }
+// block, or (k = 113 ... 128) one item per pair-of-waves block
+inline bool gram_pair_of(int k) { return k > 112 && k <= 128; }
 // waves (one work item each) per block of the one-wave Gram kernels
-#ifndef MR_GRAM_WAVES
-#define MR_GRAM_WAVES 4
-#endif
+constexpr int MR_GRAM_WAVES = 4;
 constexpr int GRAM_WAVES = MR_GRAM_WAVES;
 inline int64_t gram_blocks(int64_t n_work, int k) {
   return gram_pair_of(k) ? n_work : (n_work + GRAM_WAVES - 1) / GRAM_WAVES;

@@ -229,10 +229,7 @@ __global__ __launch_bounds__(256) void rec_exclude_kernel(uint64_t* __restrict__
 // MovieLens-like scores that is one histogram pass and one collect pass.
 // ---------------------------------------------------------------------------
 constexpr int SEL_NT = 512, SEL_CAP = 2048, SEL_D = 11, SEL_BINS = 1 << SEL_D;
-#ifndef MR_SEL_U
-#define MR_SEL_U 4
-#endif
-constexpr int SEL_U = MR_SEL_U;   // keys in flight per thread in the passes over a user's row
+constexpr int SEL_U = 4;   // keys in flight per thread in the passes over a user's row
 typedef unsigned __int128 u128;
 
 __device__ __forceinline__ u128 composite(uint64_t key, uint32_t mid) {

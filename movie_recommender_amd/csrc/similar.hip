@@ -32,10 +32,7 @@ namespace mr {
 constexpr int SM_RS = 4096;    // movies per accumulation range
 constexpr int SM_CAP = 2048;   // candidate list capacity (LDS)
 constexpr int SM_NT = 1024;    // threads per query workgroup
-#ifndef MR_SM_U
-#define MR_SM_U 4
-#endif
-constexpr int SM_U = MR_SM_U;   // (movie, rating) entries per thread in flight
+constexpr int SM_U = 4;   // (movie, rating) entries per thread in flight
 
 static unsigned sgrid(int64_t n) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384));

@@ -17,7 +17,7 @@ Cases: k in {32, 33, 48, 64, 65} x Gram chunk {2048, 64} x two rating sets:
         with repetition from items 0 .. 38 (item 39 has no ratings); at chunk
         64 the users above 64 ratings and the heavy items are split into slab
         records;
-  hash: the 400 x 300 / 30,000-draw set of tools/probes/g_hash.py.
+  hash: the 400 x 300 / 30,000-draw set of the former tools/probes/g_hash.py.
 Per case, SHA-256 of: normal_equations() of both sides after
 build_normal_equations (the unfused kernels), cg_vectors() of both sides after
 a half-step with max_iteration = 0 (the fused start: r0, p0, q0), and
