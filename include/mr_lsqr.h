@@ -97,6 +97,72 @@ int mr_lsqr_set_gather_path(mr_lsqr* ctx, int mode);
 int mr_lsqr_get_stats(mr_lsqr* ctx, mr_lsqr_stats* out);
 int mr_lsqr_reset_stats(mr_lsqr* ctx);
 
+/* Truncated SVD of the resident matrix: the k largest singular triplets by a
+ * thick-restart Golub-Kahan-Lanczos bidiagonalisation with full
+ * re-orthogonalisation (CGS2), fp64, on the context's current values.
+ *
+ * ncv: size of the Lanczos basis, k < ncv <= min(rows, cols) or ncv == k ==
+ * min(rows, cols); 0 = min(min(rows, cols), max(2k + 1, 20)).  tol >= 0: a
+ * Ritz pair is converged when its residual estimate is <= tol * sigma_1 (0:
+ * 8 ncv eps sigma_1).  maxiter: restarts at most, 0 = 10 min(rows, cols).
+ * v0_or_null[cols]: the start vector, in the space of A's COLUMNS whatever
+ * the shape (SciPy's ARPACK start vector belongs to the smaller dimension);
+ * NULL: a splitmix64 stream from `seed` mapped to (-1, 1), which also
+ * supplies the vectors that replace a breakdown.  The same inputs give the
+ * same bits.
+ *
+ * s_out[k] descending; U_out[rows * k] and Vt_out[k * cols] row-major, both
+ * NULL when want_vectors == 0.  A singular value the matrix does not have
+ * (rank < k, nnz == 0) is returned as 0 with orthonormal vectors.
+ * out->converged is 1 when k pairs converged; otherwise the first out->nconv
+ * triplets are the converged ones.  out->spmv counts products with A and A^T,
+ * out->anorm is the largest Ritz value seen, out->max_residual the largest
+ * residual estimate of the k returned pairs; mr_lsqr_svds_residuals returns
+ * the last call's k estimates.  The basis buffers, 2 (rows + cols)(ncv + 1)
+ * doubles, are allocated by the first call and grown on demand.  A single
+ * Lanczos vector finds one vector of a multiple singular value; further
+ * copies appear only through rounding.  0, or -1 on error: k or ncv out of
+ * range (min(rows, cols) == 0 admits no k), negative tol, non-finite or zero
+ * v0. */
+typedef struct mr_svds_result {
+  int converged, restarts, nconv;
+  long long spmv;
+  double anorm, max_residual;
+} mr_svds_result;
+int mr_lsqr_svds(mr_lsqr* ctx, int k, int ncv, double tol, int maxiter,
+                 const double* v0_or_null, unsigned long long seed, int want_vectors,
+                 double* s_out, double* U_out, double* Vt_out, mr_svds_result* out);
+int mr_lsqr_svds_residuals(mr_lsqr* ctx, int k, double* resid_out);
+
+/* Kernel classes of the basis kernels; the SpMVs of an SVD are timed into
+ * MR_LSQR_K_A / MR_LSQR_K_AT of mr_lsqr_stats. */
+enum {
+  MR_SVDS_K_ORTH = 0,   /* basis dot, partial sums, basis update, normalise */
+  MR_SVDS_K_COMBINE,    /* basis times a small dense matrix                 */
+  MR_SVDS_K_COUNT
+};
+typedef struct mr_svds_stats {
+  double kernel_ms[MR_SVDS_K_COUNT];
+  long long kernel_launches[MR_SVDS_K_COUNT];   /* timed intervals            */
+  long long steps;          /* Lanczos steps (one A and one A^T product each)  */
+  long long orth_bytes;     /* basis bytes the dot and update kernels read     */
+  double solve_ms;          /* wall time of the calls                          */
+} mr_svds_stats;
+int mr_svds_get_stats(mr_lsqr* ctx, mr_svds_stats* out);
+
+/* The basis kernels on host data.  mr_basis_orth: w_inout[n] orthogonalised
+ * against the n x j column-major `basis` by classical Gram-Schmidt applied
+ * twice; h_out[j] = the sum of both passes' coefficients, *norm_out = |w|
+ * after it (w is not normalised; j == 0 leaves w as it is).  mr_basis_combine:
+ * out (n x r, column-major) = basis (n x m, column-major) * Y (m x r,
+ * row-major).  mr_basis_plan: the dot / update kernels' grid for n rows and
+ * the rows one pass of that grid covers. */
+int mr_basis_orth(int device, long long n, int j, const double* basis, double* w_inout,
+                  double* h_out, double* norm_out);
+int mr_basis_combine(int device, long long n, int m, int r, const double* basis,
+                     const double* Y, double* out);
+int mr_basis_plan(long long n, long long* blocks_out, long long* rows_per_pass_out);
+
 #ifdef __cplusplus
 }
 #endif

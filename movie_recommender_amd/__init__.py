@@ -13,6 +13,8 @@ Modules
   tagcount    tag-count content model, median predictor (``include/mr_tagcount.h``)
   lsqr        general sparse LSQR and the SciPy-style ALS on it (``include/mr_lsqr.h``)
   lsmr        SciPy's LSMR on the same resident matrix, and the ALS with it
+  svds        SciPy's svds (k largest singular triplets) on the same resident matrix
+  puresvd     PureSVD: the rating matrix's truncated SVD as a served factor model
   distributed one process per GPU, users/items sharded, factor all-gather
   synth       seeded MovieLens-shaped ratings (benchmarks, statistical tests)
   build       compiles ``lib/cpp_ls_lib.so`` with hipcc for gfx950

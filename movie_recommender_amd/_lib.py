@@ -130,6 +130,32 @@ class MrLsmrResult(ctypes.Structure):
                 ("normx", ctypes.c_double)]
 
 
+SVDS_K_NAMES = ["orth", "combine"]
+
+
+class MrSvdsResult(ctypes.Structure):
+    _fields_ = [("converged", ctypes.c_int), ("restarts", ctypes.c_int),
+                ("nconv", ctypes.c_int), ("spmv", ctypes.c_longlong),
+                ("anorm", ctypes.c_double), ("max_residual", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"converged": self.converged, "restarts": self.restarts, "nconv": self.nconv,
+                "spmv": self.spmv, "anorm": self.anorm, "max_residual": self.max_residual}
+
+
+class MrSvdsStats(ctypes.Structure):
+    _fields_ = [("kernel_ms", ctypes.c_double * len(SVDS_K_NAMES)),
+                ("kernel_launches", ctypes.c_longlong * len(SVDS_K_NAMES)),
+                ("steps", ctypes.c_longlong), ("orth_bytes", ctypes.c_longlong),
+                ("solve_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"kernel_ms": {n: self.kernel_ms[i] for i, n in enumerate(SVDS_K_NAMES)},
+                "kernel_launches": {n: self.kernel_launches[i]
+                                    for i, n in enumerate(SVDS_K_NAMES)},
+                "steps": self.steps, "orth_bytes": self.orth_bytes, "solve_ms": self.solve_ms}
+
+
 class MrComm(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p),
                 ("rank", ctypes.c_int),
@@ -243,6 +269,17 @@ SIGNATURES = {
     "mr_lsqr_set_gather_path": (ctypes.c_int, [VP, ctypes.c_int]),
     "mr_lsqr_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(MrLsqrStats)]),
     "mr_lsqr_reset_stats": (ctypes.c_int, [VP]),
+    # truncated SVD on the same context (include/mr_lsqr.h)
+    "mr_lsqr_svds": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                    DP, ctypes.c_ulonglong, ctypes.c_int, DP, DP, DP,
+                                    ctypes.POINTER(MrSvdsResult)]),
+    "mr_lsqr_svds_residuals": (ctypes.c_int, [VP, ctypes.c_int, DP]),
+    "mr_svds_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(MrSvdsStats)]),
+    "mr_basis_orth": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, DP, DP, DP,
+                                     DP]),
+    "mr_basis_combine": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                                        ctypes.c_int, DP, DP, DP]),
+    "mr_basis_plan": (ctypes.c_int, [ctypes.c_longlong, LLP, LLP]),
     # factor consumers (include/mr_serving.h)
     "mr_rec_create": (VP, [ctypes.c_int, ctypes.c_int, ctypes.c_int, DP, ctypes.c_int, IP, IP,
                            DP]),

@@ -26,6 +26,7 @@
 #include "lsmr_device.h"
 #include "lsqr_device.h"
 #include "sp_structure.h"
+#include "svds_device.h"
 
 namespace mr {
 
@@ -176,6 +177,7 @@ struct Lsqr : LaunchTimer {
   LsmrState *lm = nullptr, *h_lm = nullptr;
   LsqrState* cur = nullptr;    // the running solve's state (st, or lm's head)
   int cur_mode = 0;            // 0, or LSQR_LSMR
+  SvdsWork* svds = nullptr;    // the truncated SVD's buffers (svds.hip), by its first call
   CgMirror *h_mirror = nullptr, *d_mirror = nullptr;
   int seq = 0;
   bool ptr_loads = false;
@@ -185,6 +187,7 @@ struct Lsqr : LaunchTimer {
     if (!s) return;
     (void)hipSetDevice(device);
     (void)hipStreamSynchronize(s);
+    svds_release(svds);
     for (void* q_ : owned) (void)hipFree(q_);
     if (tab) (void)hipFree(tab);
     if (h_st) (void)hipHostFree(h_st);
@@ -495,6 +498,11 @@ struct Lsqr : LaunchTimer {
 struct mr_lsqr {
   mr::Lsqr c;
 };
+
+mr::SvdsHost mr::svds_host_of(mr_lsqr* ctx) {
+  mr::Lsqr& c = ctx->c;
+  return mr::SvdsHost{c.device, c.s, &c.sp, &c, c.ptr_loads, &c.stats, &c.svds};
+}
 
 namespace {
 template <typename F>

@@ -153,6 +153,37 @@ class LsqrContext:
                    "normar": res.normar, "norma": res.norma, "conda": res.conda,
                    "normx": res.normx}
 
+    def svds(self, k=6, ncv=None, tol=0, which="LM", v0=None, maxiter=None,
+             return_singular_vectors=True, seed=0):
+        """The k largest singular triplets of the resident matrix, with
+        ``scipy.sparse.linalg.svds``'s arguments and return value (``svds``
+        module); the result struct is left in ``last_svds``."""
+        from . import svds as S
+        k, ncv, tol, maxiter, v0, want = S._check_args(self.rows, self.cols, k, ncv, tol, which,
+                                                       v0, maxiter, return_singular_vectors)
+        s = np.zeros(k, np.float64)
+        U = np.zeros((self.rows, k), np.float64) if want else None
+        Vt = np.zeros((k, self.cols), np.float64) if want else None
+        res = _lib.MrSvdsResult()
+        _lib.check(self._L.mr_lsqr_svds(
+            self._handle(), k, ncv, tol, maxiter,
+            None if v0 is None else v0.ctypes.data_as(_lib.DP), int(seed) & (2 ** 64 - 1),
+            1 if want else 0, s.ctypes.data_as(_lib.DP),
+            U.ctypes.data_as(_lib.DP) if want else None,
+            Vt.ctypes.data_as(_lib.DP) if want else None, ctypes.byref(res)), "mr_lsqr_svds")
+        resid = np.zeros(k, np.float64)
+        _lib.check(self._L.mr_lsqr_svds_residuals(self._handle(), k,
+                                                  resid.ctypes.data_as(_lib.DP)),
+                   "mr_lsqr_svds_residuals")
+        self.last_svds = dict(res.as_dict(), residuals=resid)
+        return S._finish(U, s, Vt, self.last_svds, want)
+
+    def svds_stats(self):
+        st = _lib.MrSvdsStats()
+        _lib.check(self._L.mr_svds_get_stats(self._handle(), ctypes.byref(st)),
+                   "mr_svds_get_stats")
+        return st.as_dict()
+
     def set_values(self, values):
         """New values for the same structure, in the order given at creation."""
         v = _vec(values, self.nnz, "values")
